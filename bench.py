@@ -14,13 +14,23 @@ kp_to_valid_rays is computed on the host before the timed region).
   layout (one independent frame per rank, no collective).
 Rank 0 reports the job's rays / max-over-ranks time, and per-rank render / all-gather / compose ms.
 
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line: the headline rays/s, `ms_per_step`, the per-rank phase times and the roofline
+figures that follow from the timed steps alone (the fields below that need runs of their own are null).
+`--full` adds every other leg described below (MFMA tallies, the other precisions, tau = 20, the shard
+balance projection, the other configurations, the training step, the oracle parity check and the CPU
+baseline); the `--no-*` / `--also` / `--other-configs` switches trim a `--full` run.
+`--dump-outputs DIR` writes what the last timed step returned (the render outputs in ray order and the
+composed frame) as DIR/<name>.npy, float32; the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
+
 Headline precision: fp16x4 (operands scaled by exact powers of two and split into two fp16 parts each,
 x = x0 + x1 and W = W0 + W1 within 2^-23 of |x|, |W|; all four products, fp32 accumulation: each product
 within ~2^-22 of |x W|, the bound of bf16x6's dropped terms, so fp32-accurate like bf16x6 with four
 16-bit MFMAs per 16 k instead of six).  The other modes — bf16x6 (the round-3 headline), fp16x3, fp32,
-bf16x3 — are timed on the same frame (`other_precisions`).
+bf16x3 — are timed on the same frame (`other_precisions`, `--full`).
 
-Extra JSON fields:
+Extra JSON fields (`--full`; a plain run fills only the roofline's `achieved` / `frac` / `kernel_ms`):
   roofline      dominant kernel (render_kernel, coarse + fine launch) against the peak of the MFMA
                 pipe its MLP runs on: `achieved` = the reference's algorithmic FLOPs (SURVEY §8(d):
                 1,723,648 per sample x 256 samples per ray) / the launches' time (HIP events on the
@@ -84,6 +94,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: MFMA tallies (frac_executed, frac_required), "
+                         "the other precisions, tau = 20, the shard balance projection, the other configurations, the "
+                         "training step, the oracle parity check and the CPU baseline (the switches below trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0: the render outputs in ray order and the "
+                         "composed frame) as DIR/<name>.npy, float32")
     ap.add_argument("--res", type=int, default=None, help="frame size (default 512; 1024 in pixels mode at N > 1)")
     ap.add_argument("--tau", type=float, default=79.6, help="cutoff temperature of the synthetic checkpoint")
     ap.add_argument("--joints", type=int, default=24)
@@ -112,7 +129,27 @@ def parse():
                          "ANERF_LIB_PATH is honoured by this harness, never by the package)")
     ap.add_argument("--precision", default="fp16x4", choices=["fp32", "bf16x6", "fp16x4", "fp16x3", "bf16x3"],
                     help="MLP arithmetic (include/anerf.h ANERF_PREC_*)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET = 48 << 20  # bytes of --dump-outputs in all; larger outputs are sampled by rows
+
+
+def dump_outputs(path, arrays):
+    """Write the device tensors of `arrays` as path/<name>.npy (float32).  Past DUMP_BUDGET bytes in all, every
+    array keeps the same fraction of its rows, chosen by a fixed seed (sorted; the same rows in every run)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.numel() * 4 for v in arrays.values())
+    keep = min(1.0, DUMP_BUDGET / max(total, 1))
+    for name, v in arrays.items():
+        v = v.detach().to(torch.float32).cpu().numpy()
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], max(1, int(v.shape[0] * keep)), replace=False))
+            v = v[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v))
 
 
 def traffic_from_profiles(precision):
@@ -488,6 +525,11 @@ def main():
         tdist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: render_rays' outputs (pixels mode: the
+        # all-gathered frame's) in ray order, and the composed frame
+        dump_outputs(a.dump_outputs, {**last["out"], "frame_rgb": img.view(H, W, 3), "frame_disp": dimg.view(H, W),
+                                      "frame_acc": aimg.view(H, W)})
     kern_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1, _, _ in ev]))
     phase = torch.tensor([kern_ms, float(np.mean([e1.elapsed_time(e2) for _, e1, e2, _ in ev])),
                           float(np.mean([e2.elapsed_time(e3) for _, _, e2, e3 in ev])), float(n_mine)],
@@ -507,14 +549,15 @@ def main():
     # the launches' MFMA work (kernel-side tally of one extra, untimed call over this rank's rays) and
     # the work an exact fp32 implementation must do after exact-zero window skipping: the fp32 mode's
     # tally of the same rays (v_mfma_f32_32x32x2_f32, FLOP_F32_MFMA each)
-    if a.no_tally:  # (PMC passes: no dispatch outside the timed steps)
+    tally = a.full and not a.no_tally
+    if not tally:  # (a plain run, and the PMC passes: no dispatch outside the timed steps)
         n_f32 = n_bf16 = req_f32 = None
     else:
         rc.render_rays(rb, S, skts=skts.expand(n_mine, -1, -1, -1), cyls=cyl.expand(n_mine, -1), N_importance=I,
                        chunk=4096, ret_alpha=False, count_mfma=True, near_far_given=sharded)
         torch.cuda.synchronize()
         n_f32, n_bf16 = (int(v) for v in rc.last_mfma.tolist())
-    if a.no_tally:
+    if not tally:
         pass
     elif a.precision == "fp32":
         req_f32 = n_f32
@@ -537,10 +580,10 @@ def main():
     traffic, traffic_src, prof_clock = (traffic_from_profiles(a.precision)
                                         if _config_name(H, S, I, a.joints) == "config3" else (None, None, None))
 
-    # N = 1 extras on the same frame: the other precision modes, and this mode at tau = 20 (the untrained
+    # --full, N = 1: extras on the same frame: the other precision modes, and this mode at tau = 20 (the untrained
     # value: wider cutoff windows, more live joints per block than tau = 79.6)
     others, tau20 = {}, None
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         for p in [x for x in a.also.split(",") if x and x != a.precision]:
             rcp = anerf.RayCaster(anerf.RenderConfig(n_joints=a.joints, N_samples=S, N_importance=I,
                                                      precision=p).validate(), ck, device=local)
@@ -563,24 +606,24 @@ def main():
                      "frac_executed": round(tflop / (tms * 1e-3) / 1e12 / tpeak, 4)}
             del rc20
 
-    # N = 1: the 8-rank pixel split's balance, projected on this GPU (each shard of this frame alone)
+    # --full, N = 1: the 8-rank pixel split's balance, projected on this GPU (each shard of this frame alone)
     balance = None
-    if rank == 0 and world == 1 and not a.no_balance:
+    if a.full and rank == 0 and world == 1 and not a.no_balance:
         rb_nf = rb_all.clone()
         near_far(rb_nf, cyl, chunk=4096, out=(rb_nf[:, 6], rb_nf[:, 7]))
         balance = shard_projection(rc, rb_nf, S, I, skts, cyl)
         del rb_nf
 
-    # N = 1: every other 1-GPU BASELINE configuration and the shipped mixamo configuration, same precision
+    # --full, N = 1: every other 1-GPU BASELINE configuration and the shipped mixamo configuration, same precision
     other_cfgs = {}
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         for name in [x for x in a.other_configs.split(",") if x]:
             other_cfgs[name] = other_config_leg(a, name, OTHER_CONFIGS[name], dev)
             torch.cuda.empty_cache()
 
-    # N = 1: the training step of the same path at the reference's training configuration (§8(f) row 2)
+    # --full, N = 1: the training step of the same path at the reference's training configuration (§8(f) row 2)
     training = None
-    if rank == 0 and world == 1 and not a.no_train:
+    if a.full and rank == 0 and world == 1 and not a.no_train:
         sys.path.insert(0, os.path.join(REPO, "tools"))
         import train_bench
         training = train_bench.measure(train_bench.parser().parse_args(["--steps", "10", "--warmup", "2"]), dev=dev)
@@ -592,10 +635,10 @@ def main():
         training["joints65"] = {k: t65[k] for k in ("value", "ms_per_step", "joints", "view_layout")}
         torch.cuda.empty_cache()
 
-    # parity at every N (rank 0: the all-gathered frame in pixels mode, its own frame in frames mode); the
+    # --full: parity at every N (rank 0: the all-gathered frame in pixels mode, its own frame in frames mode); the
     # CPU baseline at N = 1 only
     cpu, parity = None, None
-    if rank == 0 and not a.no_cpu:
+    if a.full and rank == 0 and not a.no_cpu:
         parity, cpu = parity_leg(a, cfg, ck, sc, cyls, idxs[0], c2w_np, H, W, last["out"], n, dev, world == 1)
 
     if rank == 0:
@@ -607,7 +650,7 @@ def main():
                   "compose_ms": round(p[2], 3)} for r, p in enumerate(per_rank)]
         line = {
             "metric": BASELINE["metric"], "value": round(value, 1), "unit": "rays/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * elapsed / a.steps, 3),
+            "steps": a.steps, "warmup": a.warmup, "full": a.full, "ms_per_step": round(1e3 * elapsed / a.steps, 3),
             "higher_is_better": True, "scaling": "strong" if sharded else "weak", "vs_baseline": None,
             "dtype": DTYPE[a.precision], "precision": a.precision,
             "data": "synthetic (seeded SMPL-24 pose + seeded 8x256 weights; no dataset/checkpoint offline)",

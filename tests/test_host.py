@@ -180,6 +180,29 @@ def test_drop_in_renders_in_the_benched_precision():
     assert config.RenderConfig().precision == bench_default
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as float32 <name>.npy; past the byte budget all arrays keep
+    the same seeded, sorted row sample, identical from call to call, and the whole dump stays within it."""
+    import torch
+    bench = importlib.import_module("bench")
+    rgb = torch.arange(3000, dtype=torch.float32).reshape(1000, 3)
+    acc = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"rgb_map": rgb, "acc_map": acc})
+    got = np.load(tmp_path / "a" / "rgb_map.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, rgb.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "acc_map.npy"), acc.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)  # of the 16,000 bytes above: a quarter of the rows
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"rgb_map": rgb, "acc_map": acc})
+    rgb_b, acc_b = np.load(tmp_path / "b" / "rgb_map.npy"), np.load(tmp_path / "b" / "acc_map.npy")
+    assert rgb_b.shape == (250, 3) and acc_b.shape == (250,)
+    assert rgb_b.nbytes + acc_b.nbytes <= 4000
+    assert np.all(np.diff(acc_b) > 0)
+    np.testing.assert_array_equal(rgb_b[:, 0], 3 * acc_b)  # the same rows of both arrays
+    np.testing.assert_array_equal(rgb_b, np.load(tmp_path / "c" / "rgb_map.npy"))
+
+
 def test_config_from_args_matches_surreal_config():
     args = types.SimpleNamespace(netdepth=8, netwidth=256, multires=7, multires_views=4, use_cutoff=True,
                                  cutoff_inputs=True, cutoff_viewdir=True, use_viewdirs=True, N_samples=64,

@@ -16,7 +16,7 @@ for r in 1 2 3; do
   for l in A B; do
     lib=$PWD/a-nerf_amd/libanerf_hip.so; [ $l = B ] && lib=$PWD/tools/ab/lib_$B.so
     for p in ${BPRECS:-bf16x6 fp16x3}; do
-      v=$(ANERF_LIB_PATH=$lib timeout -k 10 300 python bench.py --no-cpu --no-tau20 --no-train --also "" --precision $p 2>/dev/null | python -c "import json,sys;d=json.load(sys.stdin);print(d['value'], d['roofline']['kernel_ms'], d['roofline']['frac_executed'])") || exit 1
+      v=$(ANERF_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --no-cpu --no-tau20 --no-train --also "" --precision $p 2>/dev/null | python -c "import json,sys;d=json.load(sys.stdin);print(d['value'], d['roofline']['kernel_ms'], d['roofline']['frac_executed'])") || exit 1
       echo "$l $p $v"
     done
   done

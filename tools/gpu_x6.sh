@@ -10,5 +10,5 @@ done
 timeout -k 10 600 python -u -m pytest tests -q -x -m gpu -k "${TESTK:-bf16x6}" -p no:cacheprovider --timeout 120 --timeout-method thread > gpurun_out/pytest_x6.log 2>&1; rc=$?
 tail -5 gpurun_out/pytest_x6.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-timeout -k 10 300 python bench.py --no-cpu --precision ${PREC:-bf16x6} || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu --precision ${PREC:-bf16x6} || exit 1
 exit $rc
