@@ -1,0 +1,371 @@
+// anerf_iso.hip — the density grid's iso-surface as an indexed mesh, on the device (marching cubes).
+//
+// run_render.render_mesh (run_render.py:970-986) copies the fwd_type='mesh' grid to the host and runs
+// mcubes.marching_cubes over it; here the grid stays in HBM and is streamed four times:
+//
+//   anerf_isosurface_count   count_kernel    per grid point: its 3 owned edges (to +axis 0, 1, 2) that change sign
+//                                            and the triangles of its cell (case table), summed per block
+//                            scan_kernel     exclusive scan of the block sums (one workgroup, 64-bit), the totals
+//   anerf_isosurface_emit    vertex_kernel   the same classification, scanned within the block: each point's first
+//                                            vertex id to the workspace, its vertices to the output
+//                            triangle_kernel per cell: the case's triangles; the id of a vertex on an edge owned by
+//                                            another corner q = that point's stored first id + the number of q's
+//                                            crossing edges on lower axes (q's crossing mask recomputed)
+//
+// Order is part of the contract (anerf.h): vertices by (owner's linear index, axis), triangles by (cell's linear
+// index, table order) -- count -> scan -> emit, no atomics, so two runs give identical arrays.  Every pass
+// classifies through load() / inside() below on the same values (relu applied as the value is loaded), so the
+// emit passes can never produce more than the count pass counted; all output stores are guarded by the
+// capacities passed in all the same.
+//
+// A workgroup is 256 threads x 4 consecutive points (consecutive in the grid's last axis, so a wave reads 1 KB
+// runs); the neighbour rows a cell needs (+1 in axis 0 / 1) are read through the cache.  The pass is bound by
+// those reads (4 B per point per pass) and the 4 B per point of first-vertex ids.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/anerf.h"
+
+int anerf_internal_fail(int code, const char* msg);  // anerf_render.hip: sets anerf_last_error()
+
+namespace {
+
+#define ANERF_ISO_QUAL __device__ const
+#include "anerf_iso_table.inc"
+
+constexpr int NTHR = 256;               // threads per workgroup
+constexpr int ITEMS = 4;                // consecutive points per thread
+constexpr int TILE = NTHR * ITEMS;      // points per workgroup
+constexpr int ISO_FLAGS = ANERF_ISO_RELU | ANERF_ISO_FLIP;
+
+struct Grid {
+    const float* v;
+    int n0, n1, n2;
+    int s0, s1;  // strides of axes 0 and 1 (axis 2: 1)
+    int n;       // n0 n1 n2 < 2^31
+    float thr;
+    int relu;
+    int cells;   // every dimension >= 2; a grid without cells has no triangles and no vertices (anerf.h)
+};
+
+// The one load and the one predicate of every pass.  (v < 0 ? 0 : v keeps a NaN a NaN, as np.maximum does.)
+__device__ __forceinline__ float load(const Grid& g, int idx) {
+    const float v = g.v[idx];
+    return (g.relu && v < 0.f) ? 0.f : v;
+}
+__device__ __forceinline__ bool inside(const Grid& g, float v) { return v >= g.thr; }  // (a NaN is outside)
+
+struct Point {
+    int i, j, k;   // grid coordinates
+    float v0;      // value at the point
+    float va[3];   // value at the +axis neighbour (valid where the edge exists)
+    int vmask;     // bit a: the owned edge along axis a changes sign
+    int ccase;     // the cell's case, 0 where the point has no cell
+};
+
+// Classify point p: its owned edges and, when `want_case`, its cell.
+__device__ __forceinline__ Point classify(const Grid& g, int p, bool want_case) {
+    Point r;
+    r.i = p / g.s0;
+    const int rem = p - r.i * g.s0;
+    r.j = rem / g.s1;
+    r.k = rem - r.j * g.s1;
+    const bool h0 = g.cells && r.i + 1 < g.n0, h1 = g.cells && r.j + 1 < g.n1, h2 = g.cells && r.k + 1 < g.n2;
+    r.v0 = load(g, p);
+    const bool in0 = inside(g, r.v0);
+    r.vmask = 0;
+    r.ccase = 0;
+    bool ia[3] = {false, false, false};
+    if (h0) { r.va[0] = load(g, p + g.s0); ia[0] = inside(g, r.va[0]); r.vmask |= (ia[0] != in0) ? 1 : 0; }
+    if (h1) { r.va[1] = load(g, p + g.s1); ia[1] = inside(g, r.va[1]); r.vmask |= (ia[1] != in0) ? 2 : 0; }
+    if (h2) { r.va[2] = load(g, p + 1); ia[2] = inside(g, r.va[2]); r.vmask |= (ia[2] != in0) ? 4 : 0; }
+    if (want_case && h0 && h1 && h2) {
+        int c = (in0 ? 1 : 0) | (ia[0] ? 2 : 0) | (ia[1] ? 4 : 0) | (ia[2] ? 16 : 0);
+        c |= inside(g, load(g, p + g.s0 + g.s1)) ? 8 : 0;
+        c |= inside(g, load(g, p + g.s0 + 1)) ? 32 : 0;
+        c |= inside(g, load(g, p + g.s1 + 1)) ? 64 : 0;
+        c |= inside(g, load(g, p + g.s0 + g.s1 + 1)) ? 128 : 0;
+        r.ccase = c;
+    }
+    return r;
+}
+
+// The crossing mask of point q's owned edges on axes below `axis` (the rank of edge (q, axis) among q's vertices).
+__device__ __forceinline__ int lower_axis_crossings(const Grid& g, int q, int axis) {
+    if (axis == 0) return 0;
+    const int i = q / g.s0;
+    const int rem = q - i * g.s0;
+    const int j = rem / g.s1;
+    const bool in0 = inside(g, load(g, q));
+    int cnt = 0;
+    if (i + 1 < g.n0) cnt += inside(g, load(g, q + g.s0)) != in0;
+    if (axis == 2 && j + 1 < g.n1) cnt += inside(g, load(g, q + g.s1)) != in0;
+    return cnt;
+}
+
+// Exclusive scan of one int per thread over the workgroup (NTHR threads); `total` is the workgroup's sum.
+__device__ __forceinline__ int block_exclusive_scan(int x, int* lds, int& total) {
+    const int t = threadIdx.x;
+    __syncthreads();  // (lds may still be read by a previous call)
+    lds[t] = x;
+    __syncthreads();
+    int acc = x;
+    for (int d = 1; d < NTHR; d <<= 1) {
+        const int y = t >= d ? lds[t - d] : 0;
+        __syncthreads();
+        acc += y;
+        lds[t] = acc;
+        __syncthreads();
+    }
+    total = lds[NTHR - 1];
+    return acc - x;
+}
+
+__global__ __launch_bounds__(NTHR) void count_kernel(Grid g, int* __restrict__ block_counts, int nblocks) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    int nv = 0, nt = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        const long long p = first + it;
+        if (p < g.n) {
+            const Point pt = classify(g, (int)p, true);
+            nv += __popc(pt.vmask);
+            nt += ANERF_ISO_NTRI[pt.ccase];
+        }
+    }
+    int tv, tt;
+    block_exclusive_scan(nv, lds, tv);
+    block_exclusive_scan(nt, lds, tt);
+    if (threadIdx.x == 0) {
+        block_counts[blockIdx.x] = tv;
+        block_counts[nblocks + blockIdx.x] = tt;
+    }
+}
+
+// One workgroup: base[b] = sum of counts[< b] for the vertex and the triangle counts, tiles of NTHR with a carry.
+__global__ __launch_bounds__(NTHR) void scan_kernel(const int* __restrict__ block_counts, long long* __restrict__ base,
+                                                    int nblocks, long long* __restrict__ totals) {
+    __shared__ int lds[NTHR];
+    long long carry_v = 0, carry_t = 0;
+    for (int start = 0; start < nblocks; start += NTHR) {
+        const int b = start + threadIdx.x;
+        const int cv = b < nblocks ? block_counts[b] : 0;
+        const int ct = b < nblocks ? block_counts[nblocks + b] : 0;
+        int tv, tt;  // (a tile sums at most NTHR * 5 * TILE: fits an int)
+        const int ev = block_exclusive_scan(cv, lds, tv);
+        const int et = block_exclusive_scan(ct, lds, tt);
+        if (b < nblocks) {
+            base[b] = carry_v + ev;
+            base[nblocks + b] = carry_t + et;
+        }
+        carry_v += tv;
+        carry_t += tt;
+    }
+    if (threadIdx.x == 0) {
+        totals[0] = carry_v;
+        totals[1] = carry_t;
+    }
+}
+
+__global__ __launch_bounds__(NTHR) void vertex_kernel(Grid g, const long long* __restrict__ base, int* __restrict__ first_id,
+                                                      float* __restrict__ vertices, long long max_vertices) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    Point pts[ITEMS];
+    int nv = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        pts[it].vmask = 0;
+        if (first + it < g.n) {
+            pts[it] = classify(g, (int)(first + it), false);
+            nv += __popc(pts[it].vmask);
+        }
+    }
+    int total;
+    long long id = base[blockIdx.x] + block_exclusive_scan(nv, lds, total);
+    for (int it = 0; it < ITEMS; ++it) {
+        if (first + it >= g.n) break;
+        const Point& pt = pts[it];
+        first_id[first + it] = (int)id;  // (ids fit an int where the caller's capacities do, anerf.h)
+        for (int a = 0; a < 3; ++a) {
+            if (!((pt.vmask >> a) & 1)) continue;
+            if (id < max_vertices) {
+                const float t = (g.thr - pt.v0) / (pt.va[a] - pt.v0);
+                float x = (float)pt.i, y = (float)pt.j, z = (float)pt.k;
+                if (a == 0) x += t;
+                if (a == 1) y += t;
+                if (a == 2) z += t;
+                float* o = vertices + id * 3;
+                o[0] = x;
+                o[1] = y;
+                o[2] = z;
+            }
+            ++id;
+        }
+    }
+}
+
+__global__ __launch_bounds__(NTHR) void triangle_kernel(Grid g, const long long* __restrict__ base_t,
+                                                        const int* __restrict__ first_id, int* __restrict__ triangles,
+                                                        long long max_triangles, int flip) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    int cases[ITEMS];
+    int nt = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        cases[it] = 0;
+        if (first + it < g.n) {
+            cases[it] = classify(g, (int)(first + it), true).ccase;
+            nt += ANERF_ISO_NTRI[cases[it]];
+        }
+    }
+    int total;
+    long long tid = base_t[blockIdx.x] + block_exclusive_scan(nt, lds, total);
+    for (int it = 0; it < ITEMS; ++it) {
+        const int c = cases[it];
+        const int n = ANERF_ISO_NTRI[c];
+        if (n == 0) continue;
+        const int p = (int)(first + it);
+        for (int t = 0; t < n; ++t, ++tid) {
+            if (tid >= max_triangles) continue;
+            int ids[3];
+            for (int e = 0; e < 3; ++e) {
+                const int edge = ANERF_ISO_TRI[c][3 * t + e];
+                const int corner = ANERF_ISO_EDGE_CORNER[edge], axis = ANERF_ISO_EDGE_AXIS[edge];
+                const int q = p + (corner & 1) * g.s0 + ((corner >> 1) & 1) * g.s1 + ((corner >> 2) & 1);
+                ids[e] = first_id[q] + lower_axis_crossings(g, q, axis);
+            }
+            int* o = triangles + tid * 3;
+            o[0] = ids[0];
+            o[1] = flip ? ids[2] : ids[1];
+            o[2] = flip ? ids[1] : ids[2];
+        }
+    }
+}
+
+// Workspace layout: long long base[2 nblocks] | int block_counts[2 nblocks] | int first_id[n]
+struct Plan {
+    long long n;
+    int nblocks;
+    size_t off_counts, off_first, bytes;
+};
+
+bool plan(int32_t n0, int32_t n1, int32_t n2, Plan* pl) {
+    if (n0 < 1 || n1 < 1 || n2 < 1) return false;
+    const long long n = (long long)n0 * n1;  // (< 2^62)
+    if (n >= (1ll << 31) || n * n2 >= (1ll << 31)) return false;
+    pl->n = n * n2;
+    pl->nblocks = (int)((pl->n + TILE - 1) / TILE);
+    pl->off_counts = (size_t)pl->nblocks * 2 * sizeof(long long);
+    pl->off_first = pl->off_counts + (size_t)pl->nblocks * 2 * sizeof(int);
+    pl->bytes = pl->off_first + (size_t)pl->n * sizeof(int);
+    return true;
+}
+
+int check_common(const char* who, const float* grid, int32_t n0, int32_t n1, int32_t n2, int32_t flags, void* ws,
+                 size_t ws_bytes, Plan* pl, char* msg, size_t msg_len) {
+    if (!grid || !ws) {
+        snprintf(msg, msg_len, "%s: NULL grid or workspace", who);
+        return ANERF_EINVAL;
+    }
+    if (n0 < 1 || n1 < 1 || n2 < 1) {
+        snprintf(msg, msg_len, "%s: grid dimensions %d x %d x %d must be >= 1", who, n0, n1, n2);
+        return ANERF_EINVAL;
+    }
+    if (!plan(n0, n1, n2, pl)) {
+        snprintf(msg, msg_len, "%s: %d x %d x %d grid points do not fit 31 bits", who, n0, n1, n2);
+        return ANERF_EINVAL;
+    }
+    if (flags & ~ISO_FLAGS) {
+        snprintf(msg, msg_len, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ISO_FLAGS));
+        return ANERF_EINVAL;
+    }
+    if ((uintptr_t)ws % 8) {
+        snprintf(msg, msg_len, "%s: the workspace must be 8-byte aligned", who);
+        return ANERF_EINVAL;
+    }
+    if (ws_bytes < pl->bytes) {
+        snprintf(msg, msg_len, "%s: workspace of %zu bytes, %zu needed (anerf_isosurface_workspace)", who, ws_bytes,
+                 pl->bytes);
+        return ANERF_EWORKSPACE;
+    }
+    return ANERF_OK;
+}
+
+Grid make_grid(const float* grid, int32_t n0, int32_t n1, int32_t n2, const Plan& pl, float threshold, int32_t flags) {
+    Grid g;
+    g.v = grid;
+    g.n0 = n0;
+    g.n1 = n1;
+    g.n2 = n2;
+    g.s0 = n1 * n2;
+    g.s1 = n2;
+    g.n = (int)pl.n;
+    g.thr = threshold;
+    g.relu = (flags & ANERF_ISO_RELU) ? 1 : 0;
+    g.cells = (n0 > 1 && n1 > 1 && n2 > 1) ? 1 : 0;
+    return g;
+}
+
+int launched(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return ANERF_OK;
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(e));
+    return anerf_internal_fail(ANERF_EHIP, msg);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t anerf_isosurface_workspace(int32_t n0, int32_t n1, int32_t n2) {
+    Plan pl;
+    if (!plan(n0, n1, n2, &pl)) {
+        anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_workspace: dimensions must be >= 1 and n0 n1 n2 < 2^31");
+        return 0;
+    }
+    return pl.bytes;
+}
+
+int anerf_isosurface_count(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags, void* ws,
+                           size_t ws_bytes, int64_t* totals_dev, void* stream) {
+    Plan pl;
+    char msg[256];
+    const int rc = check_common("anerf_isosurface_count", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
+    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    if (!totals_dev) return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_count: NULL totals");
+    const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
+    long long* base = (long long*)ws;
+    int* counts = (int*)((char*)ws + pl.off_counts);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(count_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, counts, pl.nblocks);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(NTHR), 0, s, counts, base, pl.nblocks, (long long*)totals_dev);
+    return launched("anerf_isosurface_count");
+}
+
+int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags, void* ws,
+                          size_t ws_bytes, float* vertices, int64_t max_vertices, int32_t* triangles,
+                          int64_t max_triangles, void* stream) {
+    Plan pl;
+    char msg[256];
+    const int rc = check_common("anerf_isosurface_emit", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
+    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    if (max_vertices < 0 || max_triangles < 0 || max_vertices > 0x7fffffffll || max_triangles > 0x7fffffffll)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_emit: capacities must be in [0, 2^31)");
+    if ((max_vertices > 0 && !vertices) || (max_triangles > 0 && !triangles))
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_emit: NULL output with a non-zero capacity");
+    const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
+    const long long* base = (const long long*)ws;
+    int* first_id = (int*)((char*)ws + pl.off_first);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(vertex_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, base, first_id, vertices,
+                       (long long)max_vertices);
+    if (max_triangles > 0)
+        hipLaunchKernelGGL(triangle_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, base + pl.nblocks, first_id, triangles,
+                           (long long)max_triangles, (flags & ANERF_ISO_FLIP) ? 1 : 0);
+    return launched("anerf_isosurface_emit");
+}
+
+}  // extern "C"

@@ -174,6 +174,17 @@ class RayCaster:
                                                   _lib.stream_handle(dev)), "anerf_density_grid")
         return out
 
+    @torch.no_grad()
+    def extract_mesh(self, kps, skts, bones, radius=1.8, res=255, threshold=10., network=None, coords="unit",
+                     flip=False):
+        """run_render.render_mesh's body for one pose (run_render.py:980-985) without leaving the device: the
+        render_mesh_density grid, clamped at 0, and its iso-surface at `threshold` (isosurface.py).  Returns
+        (vertices float32 [V, 3], triangles int32 [T, 3]) device tensors; `coords`: "unit" (vertices / res - .5,
+        the reference's), "index" or "world" (isosurface.mesh_from_grid)."""
+        from .isosurface import mesh_from_grid
+        grid = self.render_mesh_density(kps, skts, bones, radius=radius, res=res, network=network)
+        return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip)
+
     def render_rays(self, ray_batch, N_samples, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,
                     raw_noise_std=0., ray_noise_std=0., verbose=False, ext_scale=0.001, pytest=False,

@@ -917,6 +917,14 @@ class StagedCaster:
         raw = self.render_pts_density(pts, kps, skts, bones, network=network, v=v)
         return raw.reshape(*grid.shape[:-1])
 
+    @torch.no_grad()
+    def extract_mesh(self, kps, skts, bones, radius=1.8, res=255, threshold=10., network=None, coords="unit",
+                     flip=False):
+        """As RayCaster.extract_mesh, on this caster's own render_mesh_density grid (it stays on the device)."""
+        from .isosurface import mesh_from_grid
+        grid = self.render_mesh_density(kps, skts, bones, radius=radius, res=res, network=network)
+        return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip)
+
 
 def _img_loss(name, x, y, reduction="mean", beta=0.1):
     """get_loss_fn / get_reg_fn (core/trainer.py:10-58, 147-170): MSE (img2mse), L1 (img2l1),

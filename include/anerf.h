@@ -22,6 +22,8 @@
  *   anerf_density_points    RayCaster.render_pts_density (fwd_type='density')  core/raycasters.py:597-648
  *   anerf_density_grid      RayCaster.render_mesh_density (fwd_type='mesh')    core/raycasters.py:579-595
  *                           (called by run_render.render_mesh)                 run_render.py:970-986
+ *   anerf_isosurface_count, mcubes.marching_cubes of run_render.render_mesh    run_render.py:983-984
+ *   anerf_isosurface_emit   (the grid's iso-surface as an indexed mesh, ABI 20)
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
  *   anerf_pose_kinematics_backward   its autograd (pose optimisation)
  *                                                                              core/utils/skeleton_utils.py:296-376
@@ -63,7 +65,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 19
+#define ANERF_ABI_VERSION 20
 
 enum {
     ANERF_OK = 0,
@@ -330,6 +332,35 @@ int anerf_density_points(const anerf_model* m, const float* pts, int64_t n_point
  * axis [res1] = float32(linspace(-radius, radius, res1)) and kp0 [3] = kps[0, 0]. */
 int anerf_density_grid(const anerf_model* m, const float* axis, int32_t res1, const float* kp0, const float* skts,
                        int32_t net, int32_t precision, float* raw_out, void* stream);
+
+/* ABI 20: the iso-surface of a float grid [n0][n1][n2] (element (i, j, k) at grid[(i n1 + j) n2 + k]) as an
+ * indexed triangle mesh -- mcubes.marching_cubes of run_render.render_mesh (run_render.py:983-984), on the
+ * device.  A sample is inside when value >= threshold (a NaN is outside).  flags:
+ *   ANERF_ISO_RELU  samples are clamped at 0 as they are read (render_mesh's np.maximum(raw_d, 0)): this moves
+ *                   the vertices, not only the classification;
+ *   ANERF_ISO_FLIP  reversed winding (by default normals point from inside to outside, dense to empty).
+ * One vertex per sign-changing grid edge, owned by the edge's lower grid point p and its axis, at
+ * p + t e_axis, t = (threshold - a) / (b - a) in fp32 (a: the value at p, b: at p + e_axis), in array-index
+ * coordinates (axis 0, 1, 2).  Vertices are ordered by (p's linear index, axis); triangles (int32 vertex ids,
+ * cases of csrc/anerf_iso_table.inc) by (cell's linear index, table order): the arrays are the same on every run.
+ * A dimension of 1 is valid and gives an empty mesh (no cells: no triangles, and no vertices either).
+ *
+ * anerf_isosurface_workspace: bytes of the scratch both calls share (0, with a message, for invalid dimensions).
+ * anerf_isosurface_count: counts into totals_dev (device, int64 [2]: vertices V, triangles T) and leaves the
+ * block offsets in ws.  The caller reads the 16 bytes of totals (the one synchronisation), allocates, and calls
+ * anerf_isosurface_emit with the SAME grid, dimensions, threshold, relu flag and ws: vertices float [V][3],
+ * triangles int32 [T][3].  max_vertices / max_triangles are the arrays' capacities in rows (in [0, 2^31); an
+ * output may be NULL where its capacity is 0): no store goes past them, rows beyond them are dropped.
+ * Both are allocation-free and asynchronous on `stream`.  ANERF_EINVAL, before any HIP call, for NULL pointers,
+ * a dimension < 1, n0 n1 n2 >= 2^31, unknown flag bits, a workspace not 8-byte aligned; ANERF_EWORKSPACE for a
+ * workspace smaller than anerf_isosurface_workspace's. */
+enum { ANERF_ISO_RELU = 1, ANERF_ISO_FLIP = 2 };
+size_t anerf_isosurface_workspace(int32_t n0, int32_t n1, int32_t n2);
+int anerf_isosurface_count(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
+                           void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream);
+int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
+                          void* ws, size_t ws_bytes, float* vertices, int64_t max_vertices, int32_t* triangles,
+                          int64_t max_triangles, void* stream);
 
 /* Pose -> skeleton transforms for n_frames frames, replacing
  *   PoseOptLayer.calculate_kinematic  core/pose_opt.py:372-445 (+ unrolled_kinematic_chain :482-521),
