@@ -12,6 +12,10 @@
 //                                            another corner q = that point's stored first id + the number of q's
 //                                            crossing edges on lower axes (q's crossing mask recomputed)
 //
+//   anerf_isosurface_normals normal_kernel  the vertex pass again, writing each vertex's normal: the grid's gradient
+//                                            (central differences, one-sided at the borders) interpolated along
+//                                            the vertex's edge with the same t, normalised (contract: anerf.h)
+//
 // Order is part of the contract (anerf.h): vertices by (owner's linear index, axis), triangles by (cell's linear
 // index, table order) -- count -> scan -> emit, no atomics, so two runs give identical arrays.  Every pass
 // classifies through load() / inside() below on the same values (relu applied as the value is loaded), so the
@@ -206,6 +210,65 @@ __global__ __launch_bounds__(NTHR) void vertex_kernel(Grid g, const long long* _
     }
 }
 
+// Central difference of the values along one axis at grid point idx (coordinate c of n >= 2 along the axis, stride
+// st), one-sided in the first and the last row (anerf.h, "vertex normals"): no index leaves the grid.
+__device__ __forceinline__ float grad_axis(const Grid& g, int idx, int c, int n, int st) {
+    if (c == 0) return load(g, idx + st) - load(g, idx);
+    if (c == n - 1) return load(g, idx) - load(g, idx - st);
+    return (load(g, idx + st) - load(g, idx - st)) * 0.5f;
+}
+
+// vertex_kernel's classification and scan again (the ids are recomputed, not read: the pass needs the count
+// pass's bases only), writing each vertex's normal instead of its position.
+__global__ __launch_bounds__(NTHR) void normal_kernel(Grid g, const long long* __restrict__ base,
+                                                      float* __restrict__ normals, long long max_vertices, int flip) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    Point pts[ITEMS];
+    int nv = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        pts[it].vmask = 0;
+        if (first + it < g.n) {
+            pts[it] = classify(g, (int)(first + it), false);
+            nv += __popc(pts[it].vmask);
+        }
+    }
+    int total;
+    long long id = base[blockIdx.x] + block_exclusive_scan(nv, lds, total);
+    for (int it = 0; it < ITEMS; ++it) {
+        if (first + it >= g.n) break;
+        const Point& pt = pts[it];
+        if (!pt.vmask) continue;
+        const int p = (int)(first + it);
+        const float g0[3] = {grad_axis(g, p, pt.i, g.n0, g.s0), grad_axis(g, p, pt.j, g.n1, g.s1),
+                             grad_axis(g, p, pt.k, g.n2, 1)};
+        for (int a = 0; a < 3; ++a) {
+            if (!((pt.vmask >> a) & 1)) continue;
+            if (id < max_vertices) {
+                const float t = (g.thr - pt.v0) / (pt.va[a] - pt.v0);
+                const int q = p + (a == 0 ? g.s0 : (a == 1 ? g.s1 : 1));
+                const float g1[3] = {grad_axis(g, q, pt.i + (a == 0), g.n0, g.s0),
+                                     grad_axis(g, q, pt.j + (a == 1), g.n1, g.s1),
+                                     grad_axis(g, q, pt.k + (a == 2), g.n2, 1)};
+                const float Gx = g0[0] + t * (g1[0] - g0[0]);
+                const float Gy = g0[1] + t * (g1[1] - g0[1]);
+                const float Gz = g0[2] + t * (g1[2] - g0[2]);
+                const float s = (Gx * Gx + Gy * Gy) + Gz * Gz;
+                float* o = normals + id * 3;
+                if (s > 0.0f && s < __builtin_inff()) {  // (a zero or non-finite G: no normal)
+                    const float len = sqrtf(s);
+                    o[0] = (flip ? Gx : -Gx) / len;
+                    o[1] = (flip ? Gy : -Gy) / len;
+                    o[2] = (flip ? Gz : -Gz) / len;
+                } else {
+                    o[0] = o[1] = o[2] = 0.0f;
+                }
+            }
+            ++id;
+        }
+    }
+}
+
 __global__ __launch_bounds__(NTHR) void triangle_kernel(Grid g, const long long* __restrict__ base_t,
                                                         const int* __restrict__ first_id, int* __restrict__ triangles,
                                                         long long max_triangles, int flip) {
@@ -263,7 +326,7 @@ bool plan(int32_t n0, int32_t n1, int32_t n2, Plan* pl) {
     return true;
 }
 
-int check_common(const char* who, const float* grid, int32_t n0, int32_t n1, int32_t n2, int32_t flags, void* ws,
+int check_common(const char* who, const float* grid, int32_t n0, int32_t n1, int32_t n2, int32_t flags, const void* ws,
                  size_t ws_bytes, Plan* pl, char* msg, size_t msg_len) {
     if (!grid || !ws) {
         snprintf(msg, msg_len, "%s: NULL grid or workspace", who);
@@ -366,6 +429,23 @@ int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2,
         hipLaunchKernelGGL(triangle_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, base + pl.nblocks, first_id, triangles,
                            (long long)max_triangles, (flags & ANERF_ISO_FLIP) ? 1 : 0);
     return launched("anerf_isosurface_emit");
+}
+
+int anerf_isosurface_normals(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
+                             const void* ws, size_t ws_bytes, float* normals, int64_t max_vertices, void* stream) {
+    Plan pl;
+    char msg[256];
+    const int rc = check_common("anerf_isosurface_normals", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
+    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    if (max_vertices < 0 || max_vertices > 0x7fffffffll)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_normals: the capacity must be in [0, 2^31)");
+    if (max_vertices > 0 && !normals)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_normals: NULL output with a non-zero capacity");
+    if (max_vertices == 0) return ANERF_OK;
+    const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
+    hipLaunchKernelGGL(normal_kernel, dim3(pl.nblocks), dim3(NTHR), 0, (hipStream_t)stream, g, (const long long*)ws,
+                       normals, (long long)max_vertices, (flags & ANERF_ISO_FLIP) ? 1 : 0);
+    return launched("anerf_isosurface_normals");
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// anerf_kernels.hpp — __global__ kernels: fused render kernel, density-only kernel, near/far + NaN fill, ray generation, composition, encoding stage.
+// anerf_kernels.hpp — __global__ kernels: fused render kernel, density-only kernel, radiance-at-points kernel, near/far + NaN fill, ray generation, composition, encoding stage.
 // Part of the single translation unit anerf_render.hip (included there, in order).
 #pragma once
 
@@ -326,6 +326,182 @@ __global__ __launch_bounds__(256, 1) void density_kernel(ModelDev M, DensityArgs
         sig += __shfl_xor(sig, 32);
         sig += net.balpha;
         if (own && hh == 0 && s_out < A.n) A.out[s_out] = sig;
+    }
+}
+
+// ======================================================================= radiance at points
+// anerf_radiance_points (RayCaster.render_pts_radiance): a whole network at arbitrary points, every point with
+// its own ray direction -- raw (rgb, sigma) as mlp_block leaves it.  The density kernel's block loop; after the
+// trunk the fused feature + view layer with the alpha head folded in, exactly as mlp_block.  The render kernel
+// factorises the view layer's direction part per ray (compute_view_factor -> G -> view_dir_part), which needs
+// the 32 samples of a block to share a ray; here the lanes form their own windowed view features and feed them
+// as B operands of f32 k-steps against the direction columns of the view weights:
+//
+//   k-step (p, t), p < NJH2, t < 3 NK:   lane half h holds joint j = p + h NJH2 (the u part's pairing, so w'_j
+//       is the value the u part stored per lane), term t = 3 k + c of the trig table (k = 0: e_c, 1 + 2f: sin,
+//       2 + 2f: cos of e_c 2^f; e = R_j d, normalised unless view_raw);
+//       A = wvdir[j][32 rb + (l & 31)][t]   (the row's TP floats are contiguous: 16-B loads)
+//       B = T_t(e_j) * (w'_j where the term is windowed, else 1) * 2^es   (0 for a padding joint)
+//   last k-step:  A = bias / framecode column (LDS, once per workgroup; half 1: 0), B = 2^es (half 1: 0).
+//
+// fp32 in every precision mode, as view_dir_part.  A pair p whose windows are exactly 0 at every point of the
+// block adds exact zeros and is skipped (wave-uniform) when every term is windowed.
+struct RadianceArgs {
+    const float* pts;    // N x 3
+    const float* dirs;   // N x 3, or 1 x 3 with dir_stride 0
+    int64_t dir_stride;  // floats between two points' directions (3 or 0)
+    int64_t n;
+    const float* skts;   // NJ x 16, one pose
+    float cam;           // framecode index (< 0: the mean code)
+    int net;
+    float* out;          // N x 4
+};
+
+__host__ __device__ inline LdsPlan make_radiance_plan(int nj, int W, int D, int njh2, bool bone_cut) {
+    LdsPlan p = make_density_plan(nj, W, D, njh2, bone_cut);
+    int o = p.total;
+    p.wv_stride = 64 * (njh2 + 1);  // per wave: the block's view windows w'_j (+ a discard row), as make_plan
+    p.wv = o; o += 4 * p.wv_stride;
+    p.g = o; o += W / 2;            // the bias / framecode column of the view layer
+    p.total = (o + 3) & ~3;
+    return p;
+}
+
+template <int RBV, int MRV>
+__device__ __forceinline__ void view_dir_points(f32x16 (&av)[RBV], const ModelDev& M, const NetDev& net,
+                                                const float* __restrict__ sk, const float* __restrict__ wvp,
+                                                const float* __restrict__ vb, float dx, float dy, float dz, int lane,
+                                                float bs) {
+    constexpr int WH = RBV * 32, NK = 1 + 2 * MRV, KC = 3 * NK, TP = (KC + 3) & ~3;
+    const int hh = lane >> 5, sl = lane & 31;
+    const int njh2 = M.njh2, nj = M.nj;
+    const int kfw = M.cutoff_inputs ? 0 : 1;            // first k term multiplied by w' (compute_view_factor)
+    const bool cull = M.cutoff_viewdir && kfw == 0;      // every term is windowed
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(net.wvdir);
+    for (int p = 0; p < njh2; ++p) {
+        const float w = wvp[p * 64 + lane];  // (0 for a padding joint or without cutoff_viewdir, u_joint)
+        if (cull && __ballot(w != 0.0f) == 0) continue;  // (a NaN window is live)
+        const int j = p + hh * njh2;
+        const bool valid = j < nj;
+        const int jc = valid ? j : 0;
+        float e[3];
+        joint_rot(sk + 12 * jc, dx, dy, dz, e[0], e[1], e[2]);
+        const float en = M.view_raw ? 1.0f : fmaxf(norm3(e[0], e[1], e[2]), 1e-12f);  // (world: R_j d itself)
+        float feat[TP];
+        const float s0 = mask_f((M.cutoff_viewdir && kfw == 0) ? w * bs : bs, valid);
+        const float s1 = mask_f(M.cutoff_viewdir ? w * bs : bs, valid);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float ec = e[c] / en;
+            feat[c] = ec * s0;
+#pragma unroll
+            for (int f = 0; f < MRV; ++f) {
+                float sn, cs;
+                sincos_rr(ec * (float)(1 << f), sn, cs);
+                // (frequencies past the model's: zero weights in the layout's padding, zero features too)
+                feat[(1 + 2 * f) * 3 + c] = f < M.mrv ? sn * s1 : 0.0f;
+                feat[(2 + 2 * f) * 3 + c] = f < M.mrv ? cs * s1 : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int rb = 0; rb < RBV; ++rb) {
+            float wa[TP];
+#pragma unroll
+            for (int q = 0; q < TP / 4; ++q) {
+                const f32x4 x = bload4_g(rs, (jc * WH + 32 * rb + sl) * TP * 4 + q * 16, 0);
+                wa[4 * q] = x[0], wa[4 * q + 1] = x[1], wa[4 * q + 2] = x[2], wa[4 * q + 3] = x[3];
+            }
+#pragma unroll
+            for (int t = 0; t < KC; ++t) av[rb] = mfma_f32_32x32x2(wa[t], feat[t], av[rb]);
+        }
+    }
+#pragma unroll
+    for (int rb = 0; rb < RBV; ++rb)
+        av[rb] = mfma_f32_32x32x2(hh ? 0.0f : vb[32 * rb + sl], hh ? 0.0f : bs, av[rb]);
+}
+
+template <int W, int MR, int PREC>
+__global__ __launch_bounds__(256, 1) void radiance_kernel(ModelDev M, RadianceArgs A, LdsPlan P) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int RB = W / 32, RBV = (W / 2) / 32, WH = W / 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
+    const NetDev& net = M.net[A.net];
+    for (int idx = tid; idx < M.nj * 12; idx += blockDim.x) lds[P.sk + idx] = A.skts[(idx / 12) * 16 + idx % 12];
+    stage_cut(M, lds + P.cut, tid);
+    stage_bias<W>(M, net, lds + P.bias, tid);
+    if (tid < WH) {  // bview + Wv_code code, in compute_view_factor's order
+        float b = net.bview[tid];
+        if (M.cfc) {
+            const int64_t row = A.cam < 0.0f ? (int64_t)M.n_codes : (int64_t)A.cam;
+            for (int m = 0; m < M.cfc; ++m) b += net.wvcode[m * WH + tid] * net.codes[row * M.cfc + m];
+        }
+        lds[P.g + tid] = b;
+    }
+    __syncthreads();
+    Stamps st;
+    float* uf = (M.skip + 1 < M.D) ? lds + P.uf + wave * P.uf_stride : nullptr;
+    float* wvp = lds + P.wv + wave * P.wv_stride;
+    const int64_t nb = (A.n + 31) / 32;
+    // (the same trip count on every wave, as density_kernel: bf16x6's mlp_trunk has a workgroup barrier per layer)
+    for (int64_t base = (int64_t)blockIdx.x * 4; base < nb; base += (int64_t)gridDim.x * 4) {
+        const bool own = base + wave < nb;
+        if constexpr (!lockstep_mode<PREC>())
+            if (!own) break;
+        const int64_t b = own ? base + wave : nb - 1;
+        const int64_t s_out = b * 32 + (lane & 31);
+        const int64_t s = s_out < A.n ? s_out : A.n - 1;  // (the ragged block's lanes redo point n - 1)
+        const float px = A.pts[3 * s], py = A.pts[3 * s + 1], pz = A.pts[3 * s + 2];
+        const float* dp = A.dirs + s * A.dir_stride;
+        const float dx = dp[0], dy = dp[1], dz = dp[2];
+        f32x16 acc[RB], h[RB];
+        JointMask mask;
+        Ring ring;
+        int es = 0;
+        int bnd = -1;
+        bool have_bnd = false;
+        const bool pre = mlp_trunk<W, MR, true, PREC>(M, net, lds + P.sk, lds + P.cut, px, py, pz, lane, lds + P.bias, uf,
+                                                      wvp, acc, h, ring, mask,
+                                                      PREC >= 3 ? net.wviewh : (PREC == 2 ? net.wview6 : net.wview), st,
+                                                      es, PREC >= 3 ? &bnd : nullptr, &have_bnd);
+        float sig = 0.0f;
+        f32x16 av[RBV];
+        if constexpr (PREC >= 3) {
+            const int es_h = es;  // the alpha head sums the last hidden layer's activations, in its units
+            mlp_layer_h3<RBV, RB, false, true, PREC == 4 ? 4 : 3>(av, acc, h, nullptr, net.wviewh, lane, ring, pre, nullptr,
+                                                                  lds + P.bias + (M.D + 1) * W, sig, es, net.ew_view,
+                                                                  M.h3_top, 60, net.wview8, have_bnd, &bnd);
+            sig *= pow2f(-es_h);
+        } else if constexpr (PREC == 2)
+            mlp_layer_x6<RBV, RB, false, true>(av, acc, h, nullptr, net.wview6, lane, ring, pre, nullptr,
+                                               lds + P.bias + (M.D + 1) * W, sig);
+        else
+            mlp_layer<RBV, RB, true, false, true>(av, acc, h, nullptr, net.wview, lane, ring, nullptr,
+                                                  lds + P.bias + (M.D + 1) * W, sig);
+        sig += __shfl_xor(sig, 32);
+        sig += net.balpha;
+        const float bs = PREC >= 3 ? pow2f(es) : 1.0f;  // (the view layer's units: the B operands carry them)
+        if (M.mrv == 0) view_dir_points<RBV, 0>(av, M, net, lds + P.sk, wvp, lds + P.g, dx, dy, dz, lane, bs);
+        else view_dir_points<RBV, 4>(av, M, net, lds + P.sk, wvp, lds + P.g, dx, dy, dz, lane, bs);
+        float rgb[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* wr = net.wrgb + (c * 2 + hh) * RBV * 16;
+            float a = 0.0f;
+#pragma unroll
+            for (int rb = 0; rb < RBV; ++rb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) a += wr[rb * 16 + i] * relu_act(av[rb][i]);
+            a += __shfl_xor(a, 32);
+            if constexpr (PREC >= 3) a *= pow2f(-es);  // (the view layer's units)
+            rgb[c] = a + net.brgb[c];
+        }
+        if (own && hh == 0 && s_out < A.n) {
+            float* o = A.out + 4 * s_out;
+            o[0] = rgb[0];
+            o[1] = rgb[1];
+            o[2] = rgb[2];
+            o[3] = sig;
+        }
     }
 }
 

@@ -876,6 +876,67 @@ int anerf_density_grid(const anerf_model* m, const float* axis, int32_t res1, co
     return launch_density(m, a, precision, stream);
 }
 
+int anerf_radiance_points(const anerf_model* m, const float* pts, int64_t n_points, const float* dirs, int64_t n_dirs,
+                          const float* skts, float cam, int32_t net, int32_t precision, float* raw_out, void* stream) {
+    // (every argument check before the first HIP call)
+    if (!m || !pts || !dirs || !skts || !raw_out) return fail(ANERF_EINVAL, "anerf_radiance_points: NULL argument");
+    if (n_points < 0) return fail(ANERF_EINVAL, "anerf_radiance_points: n_points < 0");
+    if (n_dirs != 1 && n_dirs != n_points)
+        return fail(ANERF_EINVAL, "anerf_radiance_points: n_dirs must be 1 or n_points");
+    if (m->md.staged) return fail(ANERF_EINVAL, "anerf_radiance_points: staged encoder (multires_bones > 0, relpos or rayangle kp / view inputs): the training stages serve this model, anerf.h");
+    if (precision < ANERF_PREC_FP32 || precision > ANERF_PREC_FP16X4)
+        return fail(ANERF_EINVAL, "anerf_radiance_points: unsupported precision");
+    if (net < -1 || net > 1) return fail(ANERF_EINVAL, "anerf_radiance_points: no such network");
+    if (net < 0) net = m->desc.has_fine ? 1 : 0;  // the reference's default network (raycasters.py:616-620)
+    if (net == 1 && m->desc.single_net) net = 0;  // network_fine is network_fn
+    if (net == 1 && !m->desc.has_fine) return fail(ANERF_EINVAL, "anerf_radiance_points: no such network");
+    if (m->md.cfc && !(cam < (float)m->md.n_codes))
+        return fail(ANERF_EINVAL, "anerf_radiance_points: framecode index out of range");
+    const int W = m->desc.net_width, mr = layout_multires(m->desc.multires);
+    const LdsPlan P = make_radiance_plan(m->desc.n_joints, W, m->desc.net_depth, m->njh2, m->md.bone_cut != 0);
+    if (P.total * 4 > 160 * 1024)
+        return fail(ANERF_EINVAL, "anerf_radiance_points: configuration exceeds the 160 KiB LDS budget");
+    if (!((W == 256 || W == 128 || W == 64) && (mr == 7 || mr == 10)))
+        return fail(ANERF_EINVAL, "anerf_radiance_points: no kernel instance for this width / multires");
+    if (n_points == 0) return ANERF_OK;
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != m->device) return fail(ANERF_EINVAL, "anerf_radiance_points: current device differs from the model's device");
+    RadianceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.pts = pts;
+    a.dirs = dirs;
+    a.dir_stride = n_dirs == 1 ? 0 : 3;
+    a.n = n_points;
+    a.skts = skts;
+    a.cam = cam;
+    a.net = net;
+    a.out = raw_out;
+    const int64_t nb = (a.n + 31) / 32;
+    const unsigned grid = (unsigned)std::min<int64_t>((nb + 3) / 4, 256 * 32);
+    const size_t lds_bytes = (size_t)P.total * 4;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define ANERF_LAUNCH(WW, MM)                                                                          \
+    do {                                                                                             \
+        auto kfn = precision == ANERF_PREC_BF16X3 ? radiance_kernel<WW, MM, 1>                      \
+                 : precision == ANERF_PREC_BF16X6 ? radiance_kernel<WW, MM, 2>                      \
+                 : precision == ANERF_PREC_FP16X3 ? radiance_kernel<WW, MM, 3>                      \
+                 : precision == ANERF_PREC_FP16X4 ? radiance_kernel<WW, MM, 4> : radiance_kernel<WW, MM, 0>; \
+        HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                    (int)lds_bytes));                                                \
+        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds_bytes, st, m->md, a, P);                 \
+    } while (0)
+    if (W == 256 && mr == 7) ANERF_LAUNCH(256, 7);
+    else if (W == 128 && mr == 7) ANERF_LAUNCH(128, 7);
+    else if (W == 64 && mr == 7) ANERF_LAUNCH(64, 7);
+    else if (W == 256 && mr == 10) ANERF_LAUNCH(256, 10);
+    else if (W == 128 && mr == 10) ANERF_LAUNCH(128, 10);
+    else ANERF_LAUNCH(64, 10);
+#undef ANERF_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return ANERF_OK;
+}
+
 // skeleton tables of KinArgs: parents must form a tree rooted at root_id (any index order)
 static int kin_setup(KinArgs& a, int32_t rot_dim, const int32_t* parents, int32_t n_joints, int32_t root_id,
                      const char* who) {

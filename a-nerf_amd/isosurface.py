@@ -14,6 +14,17 @@ reached only by that name -- nothing falls back to it):
   * triangles from the case table csrc/anerf_iso_table.inc (tools/gen_iso_table.py), int32 vertex ids, sorted by
     (cell's linear index, table order).  A grid with a dimension of 1 has no cells: an empty mesh.  Normals point from dense to empty; `flip` reverses the winding.
     mcubes is not installed where this was developed: its triangle order and winding were not compared.
+
+Vertex normals (`normals=True`; anerf_isosurface_normals, include/anerf.h) come from the grid's gradient, not from
+the faces (the reference's viewer accumulates face normals on the host, render_mesh.py:35-53).  The contract, again
+shared by the kernel and `isosurface_reference`; all arithmetic fp32, separately rounded:
+  * values are taken as read: relu-clamped under `relu`, and a NaN stays a NaN;
+  * the gradient at a grid point q along axis a is (f[q + e_a] - f[q - e_a]) * 0.5f in the interior,
+    f[q + e_a] - f[q] in the first row and f[q] - f[q - e_a] in the last: no index ever leaves the grid;
+  * for the vertex owned by (p, axis) with the vertex's own t: G = g(p) + t * (g(p + e_axis) - g(p)) per component;
+  * n = -G / sqrtf((Gx*Gx + Gy*Gy) + Gz*Gz), which points from dense to empty; it is negated under `flip`, so that
+    it always agrees with the winding.  Where G is zero or not finite in any component n = (0, 0, 0) (precisely:
+    unless 0 < the squared length < inf, which also covers a squared length that underflows or overflows).
 """
 import os
 import re
@@ -51,11 +62,12 @@ def _flags(relu, flip):
 
 
 @torch.no_grad()
-def isosurface(volume, threshold, relu=False, flip=False):
+def isosurface(volume, threshold, relu=False, flip=False, normals=False):
     """(vertices float32 [V, 3], triangles int32 [T, 3]) of `volume` [n0, n1, n2] at `threshold`, as device
     tensors (see the module docstring for the contract).  A CPU tensor or NumPy array is uploaded to the
     current device; the grid is read as float32.  One host read of the two totals sits between the count and
-    the emit launches; everything runs on the current stream."""
+    the emit launches; everything runs on the current stream.
+    `normals=True` returns (vertices, triangles, normals float32 [V, 3]): one more pass over the grid."""
     if isinstance(volume, np.ndarray):
         volume = np.array(volume, dtype=np.float32)  # (a copy: torch takes no read-only arrays)
     vol = torch.as_tensor(volume)
@@ -87,12 +99,31 @@ def isosurface(volume, threshold, relu=False, flip=False):
         _lib.check(lib.anerf_isosurface_emit(_lib.ptr(vol), n0, n1, n2, float(threshold), flags, _lib.ptr(ws), need,
                                              _lib.ptr(vertices), nv, _lib.ptr(triangles), nt, stream),
                    "anerf_isosurface_emit")
+        if normals:
+            nrm = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+            _lib.check(lib.anerf_isosurface_normals(_lib.ptr(vol), n0, n1, n2, float(threshold), flags, _lib.ptr(ws),
+                                                    need, _lib.ptr(nrm), nv, stream), "anerf_isosurface_normals")
+            return vertices, triangles, nrm
     return vertices, triangles
 
 
-def isosurface_reference(volume, threshold, relu=False, flip=False):
+def _grid_gradient(v):
+    """The contract's gradient of a float32 grid (every dimension >= 2): [3, n0, n1, n2]."""
+    g = np.empty((3,) + v.shape, np.float32)
+    half = np.float32(0.5)
+    for a in range(3):
+        f = np.moveaxis(v, a, 0)
+        o = np.moveaxis(g[a], a, 0)
+        o[1:-1] = (f[2:] - f[:-2]) * half
+        o[0] = f[1] - f[0]
+        o[-1] = f[-1] - f[-2]
+    return g
+
+
+def isosurface_reference(volume, threshold, relu=False, flip=False, normals=False):
     """NumPy implementation of the same contract (same table, same fp32 arithmetic, same order): the checker
-    of `isosurface`.  Returns (vertices float32 [V, 3], triangles int32 [T, 3]) as arrays."""
+    of `isosurface`.  Returns (vertices float32 [V, 3], triangles int32 [T, 3]) as arrays, and with
+    `normals=True` the vertex normals float32 [V, 3] as the third."""
     if isinstance(volume, torch.Tensor):
         volume = volume.detach().cpu().numpy()
     v = np.ascontiguousarray(volume, dtype=np.float32)
@@ -104,12 +135,17 @@ def isosurface_reference(volume, threshold, relu=False, flip=False):
     tab = load_table()
     n = v.shape
     if min(n) < 2:  # (no cells: no triangles, and no vertices, which belong to the cells around their edge)
-        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+        empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+        return empty + (np.zeros((0, 3), np.float32),) if normals else empty
+    grad = None
+    if normals:
+        with np.errstate(all="ignore"):
+            grad = _grid_gradient(v)
     with np.errstate(invalid="ignore"):
         inside = v >= thr
     lin = np.arange(v.size, dtype=np.int64).reshape(n)
     # vertices: the sign-changing edges, sorted by (owner's linear index, axis)
-    keys, pos = [], []
+    keys, pos, gvec = [], [], []
     for a in range(3):
         lo = tuple(slice(0, n[d] - 1) if d == a else slice(None) for d in range(3))
         hi = tuple(slice(1, None) if d == a else slice(None) for d in range(3))
@@ -121,6 +157,10 @@ def isosurface_reference(volume, threshold, relu=False, flip=False):
         p[:, a] = p[:, a] + t
         keys.append(lin[lo][idx] * 3 + a)
         pos.append(p)
+        if normals:  # G = g(p) + t (g(p + e_a) - g(p)), per component
+            with np.errstate(all="ignore"):
+                gvec.append(np.stack([grad[c][lo][idx] + t * (grad[c][hi][idx] - grad[c][lo][idx]) for c in range(3)],
+                                     -1).astype(np.float32).reshape(-1, 3))
     keys = np.concatenate(keys)
     order = np.argsort(keys, kind="stable")
     keys = keys[order]
@@ -144,29 +184,74 @@ def isosurface_reference(volume, threshold, relu=False, flip=False):
     triangles = (np.concatenate(tris) if tris else np.zeros((0, 3))).astype(np.int32).reshape(-1, 3)
     if flip:
         triangles = np.ascontiguousarray(triangles[:, [0, 2, 1]])
+    if normals:
+        G = np.concatenate(gvec)[order].reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            sq = (G[:, 0] * G[:, 0] + G[:, 1] * G[:, 1]) + G[:, 2] * G[:, 2]
+            ok = (sq > 0) & (sq < np.inf)
+            nrm = (G if flip else -G) / np.sqrt(sq)[:, None]
+        nrm = np.where(ok[:, None], nrm, np.float32(0)).astype(np.float32)
+        return vertices, triangles, nrm
     return vertices, triangles
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: float x / y / z per vertex, then `list uchar int vertex_indices` per face."""
-    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
-    t = triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else np.asarray(triangles)
-    v = np.ascontiguousarray(v, dtype="<f4").reshape(-1, 3)
-    t = np.ascontiguousarray(t, dtype="<i4").reshape(-1, 3)
+def _host(x, dtype):
+    x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    return np.ascontiguousarray(x, dtype=dtype).reshape(-1, 3)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: float x / y / z per vertex (then float nx / ny / nz with `normals` [V, 3], then
+    uchar red / green / blue with `colors` [V, 3]: floats in [0, 1] stored as clip(rint(255 c), 0, 255), or uint8
+    as they are), then `list uchar int vertex_indices` per face.  Without the extras: the plain x / y / z file."""
+    v = _host(vertices, "<f4")
+    t = _host(triangles, "<i4")
+    fields, props = [("xyz", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        fields.append(("c", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    rec = np.zeros(len(v), dtype=fields)
+    rec["xyz"] = v
+    if normals is not None:
+        n = _host(normals, "<f4")
+        if len(n) != len(v):
+            raise ValueError(f"write_ply: {len(n)} normals for {len(v)} vertices")
+        rec["n"] = n
+    if colors is not None:
+        c = colors.detach().cpu().numpy() if isinstance(colors, torch.Tensor) else np.asarray(colors)
+        if c.dtype != np.uint8:
+            with np.errstate(invalid="ignore"):
+                c = np.clip(np.rint(np.float32(255) * c.astype(np.float32)), 0, 255)
+            c = np.nan_to_num(c, nan=0.0).astype(np.uint8)
+        c = c.reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"write_ply: {len(c)} colours for {len(v)} vertices")
+        rec["c"] = c
     faces = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     faces["n"] = 3
     faces["i"] = t
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(v)}\n{props}"
               f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-        f.write(v.tobytes())
+        f.write(rec.tobytes())
         f.write(faces.tobytes())
 
 
-def read_ply(path):
-    """(vertices, triangles) of a file written by write_ply."""
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2",
+              "ushort": "<u2", "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4",
+              "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def read_ply(path, attributes=False):
+    """(vertices, triangles) of a file written by write_ply; the vertex properties are parsed from the header, so
+    a file with normals or colours reads the same.  `attributes=True` returns (vertices, triangles, attrs) with
+    attrs["normals"] float32 [V, 3] (nx / ny / nz) and attrs["colors"] uint8 [V, 3] (red / green / blue) where the
+    file has them."""
     with open(path, "rb") as f:
         blob = f.read()
     end = blob.index(b"end_header\n") + len(b"end_header\n")
@@ -175,44 +260,117 @@ def read_ply(path):
         raise ValueError(f"{path}: not a binary little-endian PLY")
     nv = int(re.search(r"element vertex (\d+)", head).group(1))
     nt = int(re.search(r"element face (\d+)", head).group(1))
-    v = np.frombuffer(blob, "<f4", nv * 3, end).reshape(nv, 3).copy()
-    faces = np.frombuffer(blob, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), nt, end + nv * 12)
+    fields, element = [], None
+    for line in head.splitlines():
+        w = line.split()
+        if w[:1] == ["element"]:
+            element = w[1]
+        elif w[:1] == ["property"] and element == "vertex":
+            if len(w) != 3 or w[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: unsupported vertex property {line!r}")
+            fields.append((w[2], _PLY_TYPES[w[1]]))
+    names = [n for n, _ in fields]
+    if not all(c in names for c in "xyz"):
+        raise ValueError(f"{path}: vertices without x / y / z")
+    vdt = np.dtype(fields)
+    rec = np.frombuffer(blob, vdt, nv, end)
+    v = np.stack([rec[c].astype(np.float32) for c in "xyz"], -1).reshape(nv, 3)
+    faces = np.frombuffer(blob, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), nt, end + nv * vdt.itemsize)
     if nt and not (faces["n"] == 3).all():
         raise ValueError(f"{path}: non-triangle faces")
-    return v, faces["i"].astype(np.int32).reshape(nt, 3).copy()
+    t = faces["i"].astype(np.int32).reshape(nt, 3).copy()
+    if not attributes:
+        return v, t
+    attrs = {}
+    if all(c in names for c in ("nx", "ny", "nz")):
+        attrs["normals"] = np.stack([rec[c].astype(np.float32) for c in ("nx", "ny", "nz")], -1).reshape(nv, 3)
+    if all(c in names for c in ("red", "green", "blue")):
+        attrs["colors"] = np.stack([rec[c].astype(np.uint8) for c in ("red", "green", "blue")], -1).reshape(nv, 3)
+    return v, t, attrs
 
 
-def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False):
+def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False, normals=False, colors=False,
+                   view="normal", cams=None, radiance=None):
     """extract_mesh's second half: the iso-surface of a caster's render_mesh_density grid (relu on load, as
     run_render.render_mesh's np.maximum(raw_d, 0)) in the requested coordinates:
       "index"  array-index coordinates, as mcubes.marching_cubes;
       "unit"   vertices / res - .5  (run_render.py:985);
       "world"  (lin(v1), lin(v0), lin(v2)) + kps[0, 0], lin(t) = -radius + 2 radius t / res: the grid is the
                'xy' meshgrid of anerf_density_grid, element (a, b, c) at (axis[b], axis[a], axis[c]); swapping two
-               axes mirrors the mesh, so the winding is reversed there to keep the normals pointing outward."""
+               axes mirrors the mesh, so the winding is reversed there to keep the normals pointing outward.
+    With `normals` or `colors` returns (v, t, attrs), attrs a dict of device tensors [V, 3] float32:
+      "normals"  the gradient normals (module docstring) in the frame of `coords`: as extracted for "index" and
+                 "unit", columns [1, 0, 2] for "world"; dense to empty, negated under `flip` like the winding;
+      "colors"   sigmoid of the raw rgb that `radiance(pts, dirs, cams)` (RayCaster.render_pts_radiance bound to
+                 a pose) returns at the WORLD vertices, whatever `coords`, in [0, 1].  view="normal": each vertex
+                 is looked at along its inward world normal (from outside, straight on), and where the normal is
+                 zero along the direction from the vertex to kps[0, 0]; view=(x, y, z): one direction for all.
+    An empty mesh gives (0, 3) attributes and launches nothing more."""
     if coords not in ("unit", "index", "world"):
         raise ValueError(f"coords must be 'unit', 'index' or 'world', got {coords!r}")
-    v, t = isosurface(grid, threshold, relu=True, flip=bool(flip) != (coords == "world"))
+    one_dir = None
+    if colors:
+        if radiance is None:
+            raise ValueError("colors=True needs the network: use RayCaster.extract_mesh")
+        if not (isinstance(view, str) and view == "normal"):
+            one_dir = torch.as_tensor(view, dtype=torch.float32).reshape(-1)
+            if one_dir.numel() != 3:
+                raise ValueError(f"view must be 'normal' or one direction (x, y, z), got {view!r}")
+    wflip = bool(flip) != (coords == "world")  # the winding's flag in index coordinates
+    need_n = bool(normals) or (bool(colors) and one_dir is None)
+    if need_n:
+        v, t, n = isosurface(grid, threshold, relu=True, flip=wflip, normals=True)
+    else:
+        v, t = isosurface(grid, threshold, relu=True, flip=wflip)
+        n = None
+    vi = v
     if coords == "unit":
         v = v / res - .5
-    elif coords == "world":
-        kp0 = torch.as_tensor(kps).to(v.device, torch.float32).reshape(-1, 3)[0]
-        v = (-radius + (2.0 * radius / res) * v[:, [1, 0, 2]]) + kp0
-    return v, t
+    kp0 = torch.as_tensor(kps).to(v.device, torch.float32).reshape(-1, 3)[0]
+    if coords == "world":
+        v = (-radius + (2.0 * radius / res) * vi[:, [1, 0, 2]]) + kp0
+    if not (normals or colors):
+        return v, t
+    attrs = {}
+    if normals:
+        # (the axis swap is a reflection: a vector follows it as it is, while the winding's flag was reversed for
+        # it -- so the extracted normals are negated back; 0 - n keeps a zero normal +0)
+        attrs["normals"] = (0.0 - n[:, [1, 0, 2]]) if coords == "world" else n
+    if colors:
+        if len(v) == 0:
+            attrs["colors"] = torch.zeros((0, 3), device=v.device, dtype=torch.float32)
+        else:
+            vw = v if coords == "world" else (-radius + (2.0 * radius / res) * vi[:, [1, 0, 2]]) + kp0
+            if one_dir is not None:
+                dirs = one_dir.to(v.device)
+            else:
+                inward = (n if not wflip else 0.0 - n)[:, [1, 0, 2]]  # n is dense -> empty unless wflip
+                inward = 0.0 - inward
+                zero = (inward == 0).all(-1, keepdim=True)
+                dirs = torch.where(zero, kp0 - vw, inward).contiguous()
+            raw = radiance(vw.contiguous(), dirs, cams)
+            attrs["colors"] = torch.sigmoid(raw[:, :3].to(torch.float32))
+    return v, t, attrs
 
 
 @torch.no_grad()
-def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, res=255, threshold=10.):
+def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, res=255, threshold=10.,
+                normals=False, colors=False, view="normal"):
     """Drop-in for run_render.render_mesh (run_render.py:970-986): per pose, the density grid and its iso-surface
     on the device, written to basedir/meshes/{i:03d}.ply in the reference's vertices / res - .5 coordinates.
-    Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it)."""
+    Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it).
+    `normals` / `colors` / `view`: as RayCaster.extract_mesh; the attributes go into the PLYs (nx / ny / nz,
+    red / green / blue) and the list holds (vertices, triangles, attrs)."""
     ray_caster = render_kwargs["ray_caster"]
     os.makedirs(os.path.join(basedir, "meshes"), exist_ok=True)
     kps, skts, bones = tensor_data["kp"], tensor_data["skts"], tensor_data["bones"]
+    extras = dict(normals=normals, colors=colors, view=view) if (normals or colors) else {}
     v_t_tuples = []
     for i in range(len(kps)):
-        v, t = ray_caster.extract_mesh(kps[i:i + 1], skts[i:i + 1], None if bones is None else bones[i:i + 1],
-                                       radius=radius, res=res, threshold=threshold)
-        write_ply(os.path.join(basedir, "meshes", f"{i:03d}.ply"), v, t)
-        v_t_tuples.append((v, t))
+        out = ray_caster.extract_mesh(kps[i:i + 1], skts[i:i + 1], None if bones is None else bones[i:i + 1],
+                                      radius=radius, res=res, threshold=threshold, **extras)
+        attrs = out[2] if extras else {}
+        write_ply(os.path.join(basedir, "meshes", f"{i:03d}.ply"), out[0], out[1], normals=attrs.get("normals"),
+                  colors=attrs.get("colors"))
+        v_t_tuples.append(tuple(out))
     return v_t_tuples

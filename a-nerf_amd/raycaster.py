@@ -12,7 +12,9 @@ Supported: eval-mode rendering (`perturb=0`, `raw_noise_std=0`, `ray_noise_std=0
 either way), any per-ray poses (`skts`/`cyls` may be expanded views of one pose —
 detected without copying — or genuinely per-ray), framecodes via `cams`; density-only
 queries `fwd_type='density'` / `'mesh'` (`render_pts_density` / `render_mesh_density`,
-:579-648).  Anything else raises `NotImplementedError`; nothing silently falls back to the CPU.
+:579-648); the whole network at points with their own view directions (`render_pts_radiance`, an
+extension: raw rgb + sigma, used for mesh colours) and meshes with normals / colours (`extract_mesh`).
+Anything else raises `NotImplementedError`; nothing silently falls back to the CPU.
 """
 import ctypes
 import glob
@@ -175,15 +177,63 @@ class RayCaster:
         return out
 
     @torch.no_grad()
+    def render_pts_radiance(self, pts, dirs, kps, skts, bones, cams=None, network=None):
+        """Raw network output (rgb before the sigmoid, sigma before the density activation: the reference's `raw`,
+        core/networks/nerf.py:133-148) at points, shape pts.shape[:-1] + (4,)  (anerf_radiance_points).  `dirs`
+        (broadcastable to pts from (3,)) plays the role of rays_d: point i is a sample of a ray with direction i.
+        One pose; `cams`: None (the eval-mode mean framecode) or one framecode index for the call."""
+        if self._staged is not None:
+            raise NotImplementedError("render_pts_radiance: staged encoders (multires_bones > 0, relpos / querypts "
+                                      "kp inputs, rayangle views) are served by the training stages, which have no "
+                                      "point-wise radiance query")
+        dev = torch.device(f"cuda:{self.model.device}")
+        p = torch.as_tensor(pts).to(dev, torch.float32)
+        shape = p.shape[:-1]
+        p = p.reshape(-1, 3).contiguous()
+        d = torch.as_tensor(dirs).to(dev, torch.float32)
+        if d.numel() == 3:
+            d = d.reshape(1, 3).contiguous()
+        else:
+            d = d.expand(*shape, 3).reshape(-1, 3).contiguous()
+        cam = -1.0
+        if cams is not None:
+            c = torch.as_tensor(cams).reshape(-1)
+            if c.numel() != 1:
+                raise NotImplementedError("render_pts_radiance takes one framecode index per call")
+            cam = float(c[0])
+        sk = self._one_pose(skts, dev)
+        out = torch.empty((p.shape[0], 4), device=dev, dtype=torch.float32)
+        if p.shape[0] == 0:
+            return out.reshape(*shape, 4)
+        _lib.check(_lib.load().anerf_radiance_points(self.model.handle, _lib.ptr(p), p.shape[0], _lib.ptr(d),
+                                                     d.shape[0], _lib.ptr(sk), cam,
+                                                     self._net_index(network), _lib.PRECISIONS[self.cfg.precision],
+                                                     _lib.ptr(out), _lib.stream_handle(dev)), "anerf_radiance_points")
+        return out.reshape(*shape, 4)
+
+    @torch.no_grad()
     def extract_mesh(self, kps, skts, bones, radius=1.8, res=255, threshold=10., network=None, coords="unit",
-                     flip=False):
+                     flip=False, normals=False, colors=False, view="normal", cams=None):
         """run_render.render_mesh's body for one pose (run_render.py:980-985) without leaving the device: the
         render_mesh_density grid, clamped at 0, and its iso-surface at `threshold` (isosurface.py).  Returns
         (vertices float32 [V, 3], triangles int32 [T, 3]) device tensors; `coords`: "unit" (vertices / res - .5,
-        the reference's), "index" or "world" (isosurface.mesh_from_grid)."""
+        the reference's), "index" or "world" (isosurface.mesh_from_grid).
+        With `normals` / `colors` returns (vertices, triangles, attrs): attrs["normals"] the grid-gradient vertex
+        normals in the frame of `coords`, attrs["colors"] the field's own colour sigmoid(rgb) in [0, 1] at the world
+        vertices, seen along `view` ("normal": against the vertex normal; or one (x, y, z) for all), with the
+        framecode `cams` (isosurface.mesh_from_grid).  Colours need the fused network: a staged caster raises
+        NotImplementedError for them (normals work there)."""
         from .isosurface import mesh_from_grid
+        if colors and self._staged is not None:
+            raise NotImplementedError("extract_mesh(colors=True): staged encoders (multires_bones > 0, relpos / "
+                                      "querypts kp inputs, rayangle views) have no point-wise radiance query")
         grid = self.render_mesh_density(kps, skts, bones, radius=radius, res=res, network=network)
-        return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip)
+        radiance = None
+        if colors:
+            def radiance(p, d, c):
+                return self.render_pts_radiance(p, d, kps, skts, bones, cams=c, network=network)
+        return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip, normals=normals,
+                              colors=colors, view=view, cams=cams, radiance=radiance)
 
     def render_rays(self, ray_batch, N_samples, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,

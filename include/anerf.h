@@ -24,6 +24,10 @@
  *                           (called by run_render.render_mesh)                 run_render.py:970-986
  *   anerf_isosurface_count, mcubes.marching_cubes of run_render.render_mesh    run_render.py:983-984
  *   anerf_isosurface_emit   (the grid's iso-surface as an indexed mesh, ABI 20)
+ *   anerf_isosurface_normals   per-vertex normals of that mesh from the grid's gradient (ABI 21; the reference's
+ *                           viewer accumulates face normals on the host)       render_mesh.py:35-53
+ *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
+ *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
  *   anerf_pose_kinematics_backward   its autograd (pose optimisation)
  *                                                                              core/utils/skeleton_utils.py:296-376
@@ -65,7 +69,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 20
+#define ANERF_ABI_VERSION 21
 
 enum {
     ANERF_OK = 0,
@@ -361,6 +365,38 @@ int anerf_isosurface_count(const float* grid, int32_t n0, int32_t n1, int32_t n2
 int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
                           void* ws, size_t ws_bytes, float* vertices, int64_t max_vertices, int32_t* triangles,
                           int64_t max_triangles, void* stream);
+
+/* ABI 21: vertex normals of the same mesh.  Call after anerf_isosurface_count with the SAME grid, dimensions,
+ * threshold, flags and ws, like anerf_isosurface_emit (before or after it: the pass reads the count pass's
+ * block offsets only and writes nothing to ws).  Row v of normals [V][3] belongs to vertex v of
+ * anerf_isosurface_emit: same order, same capacity rule (no store past max_vertices rows, rows beyond dropped;
+ * capacity 0: no launch), same argument checks.  The contract, shared with isosurface.isosurface_reference
+ * (all arithmetic fp32, separately rounded):
+ *   values    as read: relu-clamped under ANERF_ISO_RELU, a NaN stays a NaN;
+ *   gradient  at a grid point q along axis a: interior (f[q + e_a] - f[q - e_a]) * 0.5f, first row
+ *             f[q + e_a] - f[q], last row f[q] - f[q - e_a]; no index ever leaves the grid;
+ *   vertex    owned by (p, axis) with the emit pass's t: G = g(p) + t * (g(p + e_axis) - g(p)) per component;
+ *   normal    n = -G / sqrtf((Gx*Gx + Gy*Gy) + Gz*Gz), pointing from dense to empty, negated under
+ *             ANERF_ISO_FLIP so that it always agrees with the winding; n = (0, 0, 0) where G is zero or not
+ *             finite in any component (precisely: unless 0 < the squared length < inf, which also covers a
+ *             squared length that underflows to 0 or overflows). */
+int anerf_isosurface_normals(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
+                             const void* ws, size_t ws_bytes, float* normals, int64_t max_vertices, void* stream);
+
+/* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
+ * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /
+ * raw_fine and of the reference's `raw` (core/networks/nerf.py:133-148).  pts [n][3] world points; dirs
+ * [n_dirs][3] with n_dirs == n_points, or 1 (one direction for all points).  dirs plays the role of ray_batch
+ * columns 3:6 (rays_d) of anerf_render_rays: point i is treated as a sample of a ray with direction i -- the view
+ * input of joint j is R_j d, normalised (un-normalised under ANERF_ENC_VIEW_RAW), windowed by the point's own
+ * distance to the joint.  skts [NJ][4][4]: one pose.  cam: one framecode index for the call, truncated like
+ * .long(); negative: the eval-mode mean code; ignored without framecodes.  net / precision: as
+ * anerf_density_points (-1: the reference's default; single_net folds 1 into 0).
+ * ANERF_EINVAL, before any HIP call, for a NULL pointer, n_points < 0, n_dirs not in {1, n_points}, an unknown
+ * net or precision, a framecode index >= n_framecodes, a staged model; for a model on another device.
+ * n_points == 0 returns ANERF_OK without a launch.  No workspace, no allocation, asynchronous on `stream`. */
+int anerf_radiance_points(const anerf_model* m, const float* pts, int64_t n_points, const float* dirs, int64_t n_dirs,
+                          const float* skts, float cam, int32_t net, int32_t precision, float* raw_out, void* stream);
 
 /* Pose -> skeleton transforms for n_frames frames, replacing
  *   PoseOptLayer.calculate_kinematic  core/pose_opt.py:372-445 (+ unrolled_kinematic_chain :482-521),

@@ -6,7 +6,13 @@ The extraction's time includes its one host read of the totals between the count
 threshold is the grid's 99th percentile (the synthetic checkpoint's densities do not reach the reference's default
 of 10), so the surface has a realistic share of active cells.
 
-Prints one JSON line.  Usage: python tools/mesh_bench.py [res] [precision]"""
+The mesh attributes are two more legs: normals_ms, the normals pass alone (anerf_isosurface_normals after a count
+pass, no host read), and colors_ms, RayCaster.render_pts_radiance at the mesh's world vertices, each looked at
+against its own normal (colors_points of them) -- what extract_mesh(normals=True, colors=True) adds to the grid
+and the extraction.  Both are short, so they are timed over 20 repetitions.
+
+Prints one JSON line, and appends it to the file given with --append (the record: profiles/mesh_bench.jsonl).
+Usage: python tools/mesh_bench.py [res] [precision] [--append FILE]"""
 import importlib
 import json
 import os
@@ -36,9 +42,34 @@ def _time(fn, reps=5):
     return float(np.median(times)), out
 
 
+def _normals_leg(grid, thr):
+    """The normals pass alone: a count pass, then anerf_isosurface_normals into a buffer of the counted size."""
+    _lib = importlib.import_module("a-nerf_amd._lib")
+    lib = _lib.load()
+    n0, n1, n2 = grid.shape
+    need = lib.anerf_isosurface_workspace(n0, n1, n2)
+    ws = torch.empty(need, device=grid.device, dtype=torch.uint8)
+    totals = torch.empty(2, device=grid.device, dtype=torch.int64)
+    flags = iso.ANERF_ISO_RELU
+    _lib.check(lib.anerf_isosurface_count(_lib.ptr(grid), n0, n1, n2, thr, flags, _lib.ptr(ws), need, _lib.ptr(totals),
+                                          _lib.stream_handle(grid.device)), "anerf_isosurface_count")
+    nv = int(totals[0])
+    out = torch.empty((nv, 3), device=grid.device, dtype=torch.float32)
+    ms, _ = _time(lambda: _lib.check(lib.anerf_isosurface_normals(
+        _lib.ptr(grid), n0, n1, n2, thr, flags, _lib.ptr(ws), need, _lib.ptr(out), nv, _lib.stream_handle(grid.device)),
+        "anerf_isosurface_normals"), reps=20)
+    return ms
+
+
 def main():
-    res = int(sys.argv[1]) if len(sys.argv) > 1 else 255
-    prec = sys.argv[2] if len(sys.argv) > 2 else "fp16x4"
+    argv = list(sys.argv[1:])
+    append = None
+    if "--append" in argv:
+        i = argv.index("--append")
+        append = argv[i + 1]
+        del argv[i:i + 2]
+    res = int(argv[0]) if len(argv) > 0 else 255
+    prec = argv[1] if len(argv) > 1 else "fp16x4"
     cfg = anerf.RenderConfig(N_samples=64, N_importance=128, precision=prec).validate()
     ck = syn.make_checkpoint(13, n_joints=24, D=8, W=256, fine=True, tau=79.6)
     sc = syn.make_scene(n_joints=24, H=512, W=512, seed=13)
@@ -48,13 +79,27 @@ def main():
     thr = float(torch.quantile(grid.flatten()[:: max(1, grid.numel() // 1000000)].clamp_min(0), 0.99))
     iso_ms, (v, t) = _time(lambda: iso.isosurface(grid, thr, relu=True))
     both_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr))
+    normals_ms = _normals_leg(grid, thr)
+    vw, _, attrs = rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, coords="world", normals=True)
+    dirs = (0.0 - attrs["normals"]).contiguous()
+    colors_ms, raw = _time(lambda: rc.render_pts_radiance(vw, dirs, kps, skts, None), reps=20)
+    attrs_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, normals=True,
+                                                colors=True))
     n = (res + 1) ** 3
-    print(json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
+    line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
                       "grid_ms": round(grid_ms, 3), "isosurface_ms": round(iso_ms, 3),
                       "extract_mesh_ms": round(both_ms, 3), "isosurface_over_grid": round(iso_ms / grid_ms, 4),
                       "threshold": round(thr, 5), "vertices": int(v.shape[0]), "triangles": int(t.shape[0]),
                       "isosurface_points_per_s": round(n / (iso_ms * 1e-3), 1),
-                      "isosurface_grid_read_GBps": round(4 * n / (iso_ms * 1e-3) / 1e9, 1)}), flush=True)
+                      "isosurface_grid_read_GBps": round(4 * n / (iso_ms * 1e-3) / 1e9, 1),
+                      "normals_ms": round(normals_ms, 3), "colors_ms": round(colors_ms, 3),
+                      "colors_points": int(raw.shape[0]), "normals_over_grid": round(normals_ms / grid_ms, 4),
+                      "colors_over_grid": round(colors_ms / grid_ms, 4),
+                      "extract_mesh_normals_colors_ms": round(attrs_ms, 3)})
+    print(line, flush=True)
+    if append:
+        with open(append, "a") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
