@@ -49,27 +49,8 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BM = 128, BN = 128, NTHR = 256;
-// k columns per step of the bf16x3 single-segment forward / input-gradient instances: 32, or 64
-// (half the barriers, twice the A bytes in flight; experiment switch)
-#ifndef ANERF_GEMM_SK64
-#define ANERF_GEMM_SK64 0
-#endif
-// forward / input gradient row-tile height (experiment switch): 128 rows, two workgroups per CU; or 64
-// rows, four per CU (half the accumulators, LDS and epilogue per workgroup: more tiles in flight to
-// cover the per-tile load and store latency at K = 256)
-#ifndef ANERF_GEMM_BM
-#define ANERF_GEMM_BM 128
-#endif
-// B-fragment ring depth of the single-segment forward / input-gradient instances (2 or 4)
-#ifndef ANERF_GEMM_BD
-#define ANERF_GEMM_BD 4
-#endif
-// forward / input gradient column-tile width (round 5): 2 = 256 columns per workgroup where N % 256 == 0, 1 = 128
-// (A/B, profiles/r05j_gemm.txt: 256 columns 108.6 -> 134-139 us forward at M = 163,840, training 203 k -> 189 k:
-// one workgroup per CU instead of two exposes the staging; not kept)
-#ifndef ANERF_GEMM_CB
-#define ANERF_GEMM_CB 1
-#endif
+// (removed experiments, all slower or neutral; records under profiles/ (r04*, r05j_gemm.txt), code in 914abec:
+// 64 k columns per step, 64-row tiles, 256-column tiles, a 2-deep B ring for the single-segment instances)
 constexpr int MAXSEG = 3;
 
 struct SegD {
@@ -243,11 +224,7 @@ __global__ __launch_bounds__(NTHR, CB == 1 ? 256 / TBM : 1) void mlp_nt_kernel(N
 #pragma unroll
     for (int sg = 0; sg < NSEG; ++sg) {
         const long long ld = g.a[sg].ld;
-#ifdef ANERF_GEMM_PROBE_A  // (timing diagnostic only, wrong results: every tile reads rows 0..127, L2-hot)
-        ars[sg] = __builtin_amdgcn_make_buffer_rsrc((void*)(g.a[sg].p), 0, (int)(rows * ld * 4), 0x00020000);
-#else
         ars[sg] = __builtin_amdgcn_make_buffer_rsrc((void*)(g.a[sg].p + m0 * ld), 0, (int)(rows * ld * 4), 0x00020000);
-#endif
         arow[sg] = (unsigned)(sr * ld * 4);
         astep[sg] = (unsigned)(RPS * ld * 4);
         ast[sg] = g.a[sg].start;
@@ -386,8 +363,8 @@ __global__ __launch_bounds__(NTHR, CB == 1 ? 256 / TBM : 1) void mlp_nt_kernel(N
     // B fragments (the split weights, L2-resident) in a ring of BD k16-steps, prefetched BD - 1 steps
     // ahead: the waves' SQ counters showed them parked at s_waitcnt 45 % of the time with the B loads
     // one k16-step (12 MFMAs) ahead of their use (profiles/r04l_pmc_waves.txt); two more register sets
-    // fit the single-segment instances (ANERF_GEMM_BD; the multi-segment ones keep the 2-ring)
-    constexpr int BD = (NSEG == 1 && ANERF_GEMM_BD == 4 && CB == 1) ? 4 : 2;
+    // fit the single-segment instances (the multi-segment ones keep the 2-ring)
+    constexpr int BD = (NSEG == 1 && CB == 1) ? 4 : 2;
     RA R0, R1;
     BF f[BD];
     fetch_a(0, R0);
@@ -1000,16 +977,8 @@ constexpr int DGW_GA = 4 * DGW_PLANE + DGW_MASKB;     // the head pass: the chun
 constexpr int DGW_STAGE = DGW_GA + DGW_CH * 4;
 constexpr int DGW_BSUM = 8 * DGW_W * 4;              // 8 KB: the db column sums [8 staging rows][256]
 constexpr int DGW_LDS = 2 * DGW_STAGE + DGW_BSUM;    // 152.25 KB
-#ifndef ANERF_DGW_BD
-#define ANERF_DGW_BD 4
-#endif
-constexpr int DGW_BD = ANERF_DGW_BD;                 // W^T fragment ring depth (k16 steps)
+constexpr int DGW_BD = 4;                            // W^T fragment ring depth (k16 steps)
 static_assert((DGW_W / 16) % DGW_BD == 0, "the W^T ring runs on across chunks: its depth divides the k16 steps");
-// (ANERF_DGW_PROBE, timing diagnostics of experiment builds only, wrong results: 1 no dX MFMAs, 2 no dW MFMAs,
-// 3 no W^T loads, 4 no chunk staging after the first)
-#ifndef ANERF_DGW_PROBE
-#define ANERF_DGW_PROBE 0
-#endif
 
 struct DGWArgs {
     long long M, rows_per_wg;
@@ -1093,11 +1062,9 @@ __global__ __launch_bounds__(DGW_THR, 1) void mlp_dgw_kernel(DGWArgs g) {
             for (int p = 0; p < 2; ++p) ad[p] = tfrag(S + p * DGW_PLANE, kk, 32 * wave);
         }
         const bf16x8 bx0 = tfrag(S + 2 * DGW_PLANE, kk, 32 * ib), bx1 = tfrag(S + 3 * DGW_PLANE, kk, 32 * ib);
-        if (ANERF_DGW_PROBE != 2) {
-            f32x16 c = mfma(ad[1], bx0, aw[ib]);
-            c = mfma(ad[0], bx1, c);
-            aw[ib] = mfma(ad[0], bx0, c);
-        }
+        f32x16 c = mfma(ad[1], bx0, aw[ib]);
+        c = mfma(ad[0], bx1, c);
+        aw[ib] = mfma(ad[0], bx0, c);
     };
 
     if (stager) {
@@ -1206,7 +1173,7 @@ __global__ __launch_bounds__(DGW_THR, 1) void mlp_dgw_kernel(DGWArgs g) {
                 pin_lane();
                 // unit t / 2 of the next chunk into the other stage (free since the barrier that ended chunk s - 1),
                 // then its loads for the chunk after: a whole chunk of compute to land
-                if (ANERF_DGW_PROBE != 4 && (t & 1) == 0) {
+                if ((t & 1) == 0) {
                     if (s + 1 < nch) stage_unit((s + 1) & 1, t >> 1);
                     if (s + 2 < nch) fetch_unit(s + 2, t >> 1);
                 }
@@ -1240,14 +1207,9 @@ __global__ __launch_bounds__(DGW_THR, 1) void mlp_dgw_kernel(DGWArgs g) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) {
-#if ANERF_DGW_PROBE == 3
-                    f.v[j][p] = u32x4{vwl, vwl, vwl, (unsigned)kt};
-#else
+                for (int p = 0; p < 2; ++p)
                     f.v[j][p] = __builtin_bit_cast(
                         u32x4, __builtin_amdgcn_raw_buffer_load_b128(rwt, vwl, j * WBS * 2 + (kt * 2 + p) * 1024, 0));
-#endif
-                }
         };
         WF wf[DGW_BD];
 #pragma unroll
@@ -1269,14 +1231,12 @@ __global__ __launch_bounds__(DGW_THR, 1) void mlp_dgw_kernel(DGWArgs g) {
                 fetch_w(t + DGW_BD - 1, wf[(t + DGW_BD - 1) % DGW_BD]);
                 const bf16x8 ay0 = rfrag(S, t), ay1 = rfrag(S + DGW_PLANE, t);
                 const WF& f = wf[t % DGW_BD];
-                if (ANERF_DGW_PROBE != 1) {
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {  // small terms first
-                        const bf16x8 b0 = __builtin_bit_cast(bf16x8, f.v[j][0]), b1 = __builtin_bit_cast(bf16x8, f.v[j][1]);
-                        f32x16 c = mfma(ay1, b0, ax[j]);
-                        c = mfma(ay0, b1, c);
-                        ax[j] = mfma(ay0, b0, c);
-                    }
+                for (int j = 0; j < 2; ++j) {  // small terms first
+                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, f.v[j][0]), b1 = __builtin_bit_cast(bf16x8, f.v[j][1]);
+                    f32x16 c = mfma(ay1, b0, ax[j]);
+                    c = mfma(ay0, b1, c);
+                    ax[j] = mfma(ay0, b0, c);
                 }
                 dw_slot(S, t, ad);
             }
@@ -1394,29 +1354,8 @@ constexpr int FW_CH = 64;     // rows per chunk
 constexpr int FW_KH = 128;    // k columns per unit
 constexpr int FW_THR = 512;   // eight waves
 constexpr int FW_BD = 4;      // W fragment ring depth (k16 steps; divides a unit's 8)
-// (ANERF_FW_PROBE, timing diagnostics of experiment builds only, wrong results: 1 no MFMAs, 2 no W loads after the
-// ring's first, 3 no x loads after the first units, 4 no output stores, 5 = 3 + 4, 6 = 2 + 3 + 4, 7 = 6 + no staging
-// after the first units, 8 = 6 + no A fragment reads after the first units, 9 = 6 + no epilogue, 10 = 6 + no barriers
-// in the unit loop)
-#ifndef ANERF_FW_PROBE
-#define ANERF_FW_PROBE 0
-#endif
-// (experiment switch) 1: the compute waves store their outputs straight from the accumulators (no LDS tile, the
-// storer waves idle)
-#ifndef ANERF_FW_MAP
-#define ANERF_FW_MAP 0
-#endif
-// (experiment switch) 1: the MFMAs of a k16 step interleaved over the four accumulators
-#ifndef ANERF_FW_IL
-#define ANERF_FW_IL 0
-#endif
-// (experiment switch) s_setprio of the compute waves (0: none)
-#ifndef ANERF_FW_PRIO
-#define ANERF_FW_PRIO 0
-#endif
-#ifndef ANERF_FW_DIRECT
-#define ANERF_FW_DIRECT 0
-#endif
+// (removed experiments, none adopted, code in 914abec: compute roles on the odd hardware waves, the MFMAs of a k16
+// step interleaved over the accumulators, s_setprio of the compute waves, outputs stored straight from the accumulators)
 template <int NPL>
 struct FWGeo {
     static constexpr int PLANE = FW_CH * FW_KH * 2;  // 16 KB
@@ -1450,9 +1389,7 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
     using G = FWGeo<NPL>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds8[];
     float* const otile = reinterpret_cast<float*>(lds8 + 2 * G::STAGE);  // [64][256]
-    // (ANERF_FW_MAP 1, experiment: the roles on the odd (compute) and even hardware waves instead of 4-7 / 0-3)
-    const int hw = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int wave = ANERF_FW_MAP ? ((hw & 1) ? 4 + (hw >> 1) : (hw >> 1)) : hw;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lane = (int)threadIdx.x & 63, tid = wave * 64 + lane;
     const long long M = g.M;
     const long long mlo = (long long)blockIdx.x * g.rows_per_wg;
@@ -1489,7 +1426,6 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
         constexpr int NS = NSEG == 2 ? 1 : 2;
         f32x4 RR[NS][8][2];
         auto fetch = [&](int u, f32x4 (&R)[8][2]) __attribute__((always_inline)) {
-            if ((ANERF_FW_PROBE == 3 || ANERF_FW_PROBE >= 5) && u >= 2) return;
             const int s = u / nu, kh = u - s * nu;
             const long long r0 = mlo + (long long)s * FW_CH;
             const int rows = chunk_rows(s);
@@ -1542,7 +1478,6 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
             ba = g.ba[0];
         }
         auto stage = [&](int u, int buf, const f32x4 (&R)[8][2]) __attribute__((always_inline)) {
-            if (ANERF_FW_PROBE == 7 && u >= 2) return;
             unsigned char* const S = lds8 + buf * G::STAGE;
             const int s = u / nu, kh = u - s * nu;
 #pragma unroll
@@ -1608,7 +1543,7 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
             constexpr int SET = NS == 2 ? Q : 0;
             if (u + 1 < nun) stage(u + 1, Q, RR[SET]);
             fetch(u + 1 + NS, RR[SET]);
-            if (ANERF_FW_PROBE != 10) __syncthreads();
+            __syncthreads();
         };
         for (int u = 0; u < nun; u += 2) {
             body(u, std::integral_constant<int, 0>{});
@@ -1624,7 +1559,6 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
         const long long ldy = g.ldy;
         const int nval = g.nval;
         auto copy_out = [&](int s) __attribute__((always_inline)) {
-            if (ANERF_FW_PROBE == 4 || ANERF_FW_PROBE >= 5 || ANERF_FW_DIRECT) return;
             const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(yp + (mlo + (long long)s * FW_CH) * ldy), 0, (int)(chunk_rows(s) * ldy * 4), 0x00020000);
             const int c4 = 4 * (t & 63), rq = t >> 6;
@@ -1639,21 +1573,13 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
         __syncthreads();
         for (int u = 0; u < nun; ++u) {
             if (u >= nu && u % nu == 0) copy_out(u / nu - 1);
-            if (ANERF_FW_PROBE != 10) __syncthreads();
+            __syncthreads();
         }
         if (nch > 0) copy_out(nch - 1);
     } else {
         // ------------------------------------------------------------------ compute waves
         const int xw = wave - 4;  // output columns 64 xw .. 64 xw + 63: blocks 2 xw, 2 xw + 1
-#if ANERF_FW_PRIO
-        // (experiment) the compute waves' instruction issue ahead of the loader / storer waves' on the same SIMD
-        __builtin_amdgcn_s_setprio(ANERF_FW_PRIO);
-#endif
         const unsigned short* const wp = g.w;
-#if ANERF_FW_DIRECT
-        float* const ypc = yp;
-        const long long ldyc = g.ldy;
-#endif
         const int nk = g.nk, ku = 8 * nu;   // W's k16 steps; k16 steps of a chunk's units
         const int WBS = ((g.K + 15) / 16) * NPL * 512;  // elements per 32-column block of the split W
         const __amdgpu_buffer_rsrc_t rw =
@@ -1665,7 +1591,6 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
         // global k16 index q = 8 u + t: the chunk's step q % ku; steps past W's (the last unit's padding, whose
         // A columns are zero) are neither loaded nor multiplied
         auto fetch_w = [&](int q, WF& f) {
-            if ((ANERF_FW_PROBE == 2 || ANERF_FW_PROBE >= 6) && q >= FW_BD) return;
             int kt = q % ku;
             kt = kt < nk ? kt : nk - 1;  // (a straight-line instruction stream: the padding steps reload the last)
 #pragma unroll
@@ -1708,25 +1633,11 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
             for (int t = 0; t < FW_KH / 16; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
                 fetch_w(8 * u + t + FW_BD - 1, wf[(t + FW_BD - 1) % FW_BD]);  // ((8 u + t) % FW_BD = t % FW_BD)
-                if (t + 1 < FW_KH / 16 && (ANERF_FW_PROBE != 8 || u < 2)) read_a(t + 1, A[(t + 1) & 1]);
+                if (t + 1 < FW_KH / 16) read_a(t + 1, A[(t + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                if (8 * kh + t >= nk || ANERF_FW_PROBE == 1) continue;
+                if (8 * kh + t >= nk) continue;
                 const bf16x8 (&a)[NPL][2] = A[t & 1];
                 const WF& f = wf[t % FW_BD];
-#if ANERF_FW_IL
-                // (experiment) the four accumulators' chains interleaved product by product (each accumulator's own
-                // product order unchanged: the same bits)
-                constexpr int NPR = NPL == 3 ? 6 : 3;
-                constexpr int PA[6] = {NPL == 3 ? 2 : 1, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-                constexpr int O = NPL == 3 ? 0 : 3;
-#pragma unroll
-                for (int q = 0; q < NPR; ++q)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-                            acc[i][j] = mfma(a[PA[O + q]][i], __builtin_bit_cast(bf16x8, f.v[j][PB[O + q]]), acc[i][j]);
-#else
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     bf16x8 b[NPL];
@@ -1745,38 +1656,23 @@ __global__ __launch_bounds__(FW_THR, 1) void mlp_fwd_kernel(FWArgs g) {
                         acc[i][j] = mfma(a[0][i], b[0], c);
                     }
                 }
-#endif
             }
             if (kh == nu - 1) {  // the chunk's output: + bias (, relu), into the tile (its previous copy left before
                                  // the barrier that ended unit u - 1)
-#if ANERF_FW_DIRECT
-                // (experiment) straight from the accumulators to HBM: a wave instruction writes two 128 B row pieces;
-                // the descriptor ends at the chunk's last row
-                const int s = u / nu;
-                const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-                    (void*)(ypc + (mlo + (long long)s * FW_CH) * ldyc), 0, (int)(chunk_rows(s) * ldyc * 4), 0x00020000);
-#endif
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            if (ANERF_FW_PROBE == 9) continue;
                             const int row = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                             float v = acc[i][j][r];
                             v += j ? b1 : b0;
                             if (relu) v = fmaxf(v, 0.0f);
-#if ANERF_FW_DIRECT
-                            __builtin_amdgcn_raw_buffer_store_b32(
-                                __builtin_bit_cast(unsigned, v), rd,
-                                (unsigned)((row * ldyc + 64 * xw + 32 * j + (lane & 31)) * 4), 0, 0);
-#else
                             otile[row * FW_W + 64 * xw + 32 * j + (lane & 31)] = v;
-#endif
                         }
             }
-            if (ANERF_FW_PROBE != 10) __syncthreads();
+            __syncthreads();
         }
     }
 }
@@ -1844,14 +1740,11 @@ int set_segs(const anerf_seg* in, int n, int total, SegD* out) {
     return ANERF_OK;
 }
 
-// weight-gradient workgroups per launch (experiment switch): ~512 = two per CU; fewer slabs write and re-read fewer
-// partial tiles
-#ifndef ANERF_WGRAD_WG
-#define ANERF_WGRAD_WG 512
-#endif
+// weight-gradient workgroups per launch: ~512 = two per CU; fewer slabs write and re-read fewer partial tiles
+constexpr int WGRAD_WG = 512;
 int wgrad_plan(int64_t m, int32_t n, int32_t k, int* splits, long long* rows) {
     const int tiles = ((n + BN - 1) / BN) * ((k + BM - 1) / BM);
-    long long s = (ANERF_WGRAD_WG + tiles - 1) / tiles;  // ~ANERF_WGRAD_WG workgroups
+    long long s = (WGRAD_WG + tiles - 1) / tiles;  // ~WGRAD_WG workgroups
     const long long smax = (m + 255) / 256;         // >= 256 rows per slab
     if (s > smax) s = smax;
     if (s < 1) s = 1;
@@ -1977,13 +1870,8 @@ int anerf_mlp_gemm_rows(int64_t m, int32_t n, int32_t k, const anerf_seg* a, int
     }
     if (start != n) return anerf_internal_fail(ANERF_EINVAL, "output segments do not add up to n");
     g.nc = n_c;
-    // row-tile height: 128, or (ANERF_GEMM_BM 64) 64 for the single-segment instances
-    // (the fp16x4 instance is always 128 rows high)
-    const int tbm = (ANERF_GEMM_BM == 64 && n_a == 1 && !f16) ? 64 : 128;
-    // 256-column tiles (CB 2) where the columns are whole 256s (the trunk and view-input layers at W 256)
-    const int cb = (ANERF_GEMM_CB == 2 && !f16 && tbm == 128 && n % 256 == 0) ? 2 : 1;
-    g.tiles_n = (n + NBN * cb - 1) / (NBN * cb);
-    const long long tiles = (long long)((m + tbm - 1) / tbm) * g.tiles_n;
+    g.tiles_n = (n + NBN - 1) / NBN;  // 128 x 128 tiles
+    const long long tiles = (long long)((m + BM - 1) / BM) * g.tiles_n;
     if (tiles > 0x7fffffff) return anerf_internal_fail(ANERF_EINVAL, "anerf_mlp_gemm: too many tiles");
     g.total = (int)tiles;
     g.rin = rowmax_in;
@@ -2002,18 +1890,10 @@ int anerf_mlp_gemm_rows(int64_t m, int32_t n, int32_t k, const anerf_seg* a, int
     }
 #define ANERF_NT_LAUNCH(P, S)                                                                         \
     if (npl == P && n_a == S) {                                                                       \
-        constexpr int TB = (ANERF_GEMM_BM == 64 && S == 1) ? 64 : 128;                                \
-        constexpr int SKT = (ANERF_GEMM_SK64 && P == 2 && S == 1) ? 64 : 32;                          \
-        constexpr int LB = NTGeo<P, TB, SKT>::LDS_BYTES;                                              \
-        if (TB == 128 && cb == 2) {                                                                   \
-            e = nt_attr<P, S, TB, SKT, false, 2>();                                                   \
-            if (e != hipSuccess) return anerf_internal_fail(ANERF_EHIP, hipGetErrorString(e));        \
-            hipLaunchKernelGGL((mlp_nt_kernel<P, S, TB, SKT, false, 2>), dim3((unsigned)tiles), dim3(NTHR), LB, st, g); \
-        } else {                                                                                      \
-            e = nt_attr<P, S, TB, SKT>();                                                             \
-            if (e != hipSuccess) return anerf_internal_fail(ANERF_EHIP, hipGetErrorString(e));        \
-            hipLaunchKernelGGL((mlp_nt_kernel<P, S, TB, SKT>), dim3((unsigned)tiles), dim3(NTHR), LB, st, g); \
-        }                                                                                             \
+        constexpr int LB = NTGeo<P, 128, 32>::LDS_BYTES;                                              \
+        e = nt_attr<P, S, 128, 32>();                                                                 \
+        if (e != hipSuccess) return anerf_internal_fail(ANERF_EHIP, hipGetErrorString(e));            \
+        hipLaunchKernelGGL((mlp_nt_kernel<P, S, 128, 32>), dim3((unsigned)tiles), dim3(NTHR), LB, st, g); \
     }
     ANERF_NT_LAUNCH(3, 1)
     ANERF_NT_LAUNCH(3, 2)

@@ -3,12 +3,6 @@
 #pragma once
 
 // ======================================================================= fused render kernel
-#ifndef ANERF_BLOCK_SORT
-#define ANERF_BLOCK_SORT 1  // (0: blocks in ray order; tools/build_ab.sh experiments)
-#endif
-#ifndef ANERF_PERSIST
-#define ANERF_PERSIST 1  // persistent workgroups over XCD-banded queues (+3.6 % fp16x4, bit-identical; 0: one workgroup per item)
-#endif
 // The rays [ray0, ray0 + R) of one workgroup: both passes (or the launch's one) end to end.
 template <int W, int MR, int PREC>
 __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs& A, const LdsPlan& P,
@@ -90,7 +84,7 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
         };
         int* const bcnt = reinterpret_cast<int*>(lds + P.bord);
         int* const bord = bcnt + P.bord_n;
-        if constexpr (lockstep_mode<PREC>() && ANERF_BLOCK_SORT) {
+        if constexpr (lockstep_mode<PREC>()) {
             // bf16x6: the four waves meet at a workgroup barrier before every hidden layer (L1 sharing of
             // the weight stream), where a wave whose block has fewer live joints waits for the others
             // (5.8 % of the wave-cycles, profiles/r04c_stamps_bf16x6.txt).  The blocks of the workgroup
@@ -122,7 +116,7 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
             if constexpr (!lockstep_mode<PREC>())  // (no workgroup barrier inside: a wave without a block is done)
                 if (!own) break;
             const int bi = own ? it * 4 + wave : nbt - 1;
-            const int b = (lockstep_mode<PREC>() && ANERF_BLOCK_SORT) ? bord[bi] : bi;
+            const int b = lockstep_mode<PREC>() ? bord[bi] : bi;
             const int r = b / nb, s0 = (b % nb) * 32;
             const float* zr = block_z(r);
             float* rawr = lds + P.raw + P.raw_stride * r + (only_new ? 4 * S : 0);
@@ -213,41 +207,37 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
     STAMP_FLUSH(st, A.stamps);
 }
 
-// One launch of the render pass(es).  ANERF_PERSIST (default): as many workgroups as are resident at
+// One launch of the render pass(es): as many workgroups as are resident at
 // once (the host sizes the grid by occupancy), each taking R-ray items from eight queues, queue g = the
 // g-th contiguous band of the ray list, starting with its own (blockIdx & 7: workgroups b and b + 8
 // share an XCD under the round-robin dispatch — a locality choice only, correctness does not depend on
 // it) and stealing from the others when it is empty, so each XCD's L2 sees the live joints of one band
 // of the frame while the stealing evens out the bands' different costs (round 3's static XCD bands
 // lost 5 % to exactly that imbalance); +3.6 % fp16x4, outputs bit-identical (an item's arithmetic does
-// not depend on the workgroup that runs it).  ANERF_PERSIST 0: workgroup b renders rays [b R, b R + R).
+// not depend on the workgroup that runs it; one workgroup per item: removed, code in 914abec).
 template <int W, int MR, int PREC>
 __global__ __launch_bounds__(256, 1) void render_kernel(ModelDev M, RenderArgs A, LdsPlan P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if constexpr (!ANERF_PERSIST) {
-        render_item<W, MR, PREC>(M, A, P, lds, (int64_t)blockIdx.x * A.R);
-    } else {
-        const int64_t items = (A.n + A.R - 1) / A.R;
-        int* const slot = reinterpret_cast<int*>(lds + P.bord) + 2 * P.bord_n;
-        const int g0 = blockIdx.x & 7;
-        for (;;) {
-            if (threadIdx.x == 0) {
-                int64_t item = -1;
-                for (int k = 0; k < 8 && item < 0; ++k) {
-                    const int g = (g0 + k) & 7;
-                    const int64_t b0 = items * g / 8, b1 = items * (g + 1) / 8;
-                    if (b1 <= b0) continue;
-                    const unsigned t = atomicAdd(A.queue + g, 1u);
-                    if ((int64_t)t < b1 - b0) item = b0 + t;
-                }
-                slot[0] = (int)item;
+    const int64_t items = (A.n + A.R - 1) / A.R;
+    int* const slot = reinterpret_cast<int*>(lds + P.bord) + 2 * P.bord_n;
+    const int g0 = blockIdx.x & 7;
+    for (;;) {
+        if (threadIdx.x == 0) {
+            int64_t item = -1;
+            for (int k = 0; k < 8 && item < 0; ++k) {
+                const int g = (g0 + k) & 7;
+                const int64_t b0 = items * g / 8, b1 = items * (g + 1) / 8;
+                if (b1 <= b0) continue;
+                const unsigned t = atomicAdd(A.queue + g, 1u);
+                if ((int64_t)t < b1 - b0) item = b0 + t;
             }
-            __syncthreads();
-            const int item = slot[0];
-            if (item < 0) break;
-            render_item<W, MR, PREC>(M, A, P, lds, (int64_t)item * A.R);
-            __syncthreads();
+            slot[0] = (int)item;
         }
+        __syncthreads();
+        const int item = slot[0];
+        if (item < 0) break;
+        render_item<W, MR, PREC>(M, A, P, lds, (int64_t)item * A.R);
+        __syncthreads();
     }
 }
 
@@ -408,7 +398,7 @@ __device__ __forceinline__ void view_dir_points(f32x16 (&av)[RBV], const ModelDe
             float wa[TP];
 #pragma unroll
             for (int q = 0; q < TP / 4; ++q) {
-                const f32x4 x = bload4_g(rs, (jc * WH + 32 * rb + sl) * TP * 4 + q * 16, 0);
+                const f32x4 x = bload4(rs, (jc * WH + 32 * rb + sl) * TP * 4 + q * 16, 0);
                 wa[4 * q] = x[0], wa[4 * q + 1] = x[1], wa[4 * q + 2] = x[2], wa[4 * q + 3] = x[3];
             }
 #pragma unroll
@@ -457,19 +447,17 @@ __global__ __launch_bounds__(256, 1) void radiance_kernel(ModelDev M, RadianceAr
         JointMask mask;
         Ring ring;
         int es = 0;
-        int bnd = -1;
-        bool have_bnd = false;
         const bool pre = mlp_trunk<W, MR, true, PREC>(M, net, lds + P.sk, lds + P.cut, px, py, pz, lane, lds + P.bias, uf,
                                                       wvp, acc, h, ring, mask,
                                                       PREC >= 3 ? net.wviewh : (PREC == 2 ? net.wview6 : net.wview), st,
-                                                      es, PREC >= 3 ? &bnd : nullptr, &have_bnd);
+                                                      es);
         float sig = 0.0f;
         f32x16 av[RBV];
         if constexpr (PREC >= 3) {
             const int es_h = es;  // the alpha head sums the last hidden layer's activations, in its units
             mlp_layer_h3<RBV, RB, false, true, PREC == 4 ? 4 : 3>(av, acc, h, nullptr, net.wviewh, lane, ring, pre, nullptr,
                                                                   lds + P.bias + (M.D + 1) * W, sig, es, net.ew_view,
-                                                                  M.h3_top, 60, net.wview8, have_bnd, &bnd);
+                                                                  M.h3_top);
             sig *= pow2f(-es_h);
         } else if constexpr (PREC == 2)
             mlp_layer_x6<RBV, RB, false, true>(av, acc, h, nullptr, net.wview6, lane, ring, pre, nullptr,

@@ -14,23 +14,8 @@ __device__ __forceinline__ f32x2 bload2(__amdgpu_buffer_rsrc_t rs, int voff, int
 __device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
 }
-// Non-temporal (nt, cache-policy bit 2 on gfx950) forms for the weight streams an XCD's L2 should not
-// keep: the per-joint windowed parts (touched only for the block's live joints) and the view-direction
-// rows of G (once per ray and pass).  Cached like the hidden layers' streams, these push one net's
-// touched set (4.3 MB in bf16x6) past the 4 MB L2, and the cyclic hidden-layer stream then misses
-// (tools/probe/layer_probe_x6: 90 % of the MFMA rate up to a 3.8 MB footprint, 84 % at 4.2 MB).
-#ifndef ANERF_NT_V
-#define ANERF_NT_V 0
-#endif
-#ifndef ANERF_NT_G
-#define ANERF_NT_G 0
-#endif
-__device__ __forceinline__ f32x2 bload2_v(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, ANERF_NT_V ? 2 : 0));
-}
-__device__ __forceinline__ f32x4 bload4_g(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, ANERF_NT_G ? 2 : 0));
-}
+// (removed experiment, not adopted, code in 914abec: non-temporal loads of the windowed-joint and view-direction
+// weight streams, to keep them out of the XCD's L2)
 
 template <int RB>
 __device__ __forceinline__ void load_bias(f32x16 (&acc)[RB], const float* __restrict__ bp_lds, int hh) {
@@ -276,11 +261,6 @@ __device__ __forceinline__ void split3_pair(float a, float b, X6T& t, int q) {
 // value pair p (0..7) of a 16-value input block: k16-step p >> 2, dword p & 3
 __device__ __forceinline__ void split3_block_pair(const f32x16& hb, X6T (&t)[2], int p) {
     const int s = p >> 2, q = p & 3;
-#if ANERF_X6_PROBE == 2  // (diagnostic builds of tools/probe only: no split arithmetic)
-    const float v = hb[8 * s + 2 * q];
-    t[s].d[0][q] = t[s].d[1][q] = t[s].d[2][q] = __builtin_bit_cast(unsigned, v);
-    return;
-#endif
     split3_pair(hb[8 * s + 2 * q], hb[8 * s + 2 * q + 1], t[s], q);
 }
 
@@ -289,12 +269,7 @@ __device__ __forceinline__ void split3_block_pair(const f32x16& hb, X6T (&t)[2],
 // fp16x3 +0.4 % with at most three VALU per gap (two: +1.1 %); the same pin on u_part_x6: -0.1 %.
 // The fp16 layers (round 4, with the fp16x4 four-MFMA groups): two VALU per gap +0.85 % fp16x4 over
 // three, fp16x3 neutral; one +0.55 %, four +0.2 %, five -0.8 % (profiles/r04h3il_ab*.txt)
-#ifndef ANERF_X6_IL
-#define ANERF_X6_IL 3
-#endif
-#ifndef ANERF_H3_IL
-#define ANERF_H3_IL 2
-#endif
+constexpr int X6_IL = 3, H3_IL = 2;
 // One x6 group's issue order: each of the six MFMAs followed by at most one weight load and three
 // VALU instructions (the split / relu / bias work of the group), so no MFMA gap carries more than
 // the ~5 single-issue instructions an MFMA of this shape hides (MI355X_MICROARCH.md).
@@ -309,9 +284,7 @@ __device__ __forceinline__ void group_schedule() {
     }
 }
 __device__ __forceinline__ void x6_group_schedule() {
-#if ANERF_X6_IL
-    group_schedule<6, 3, 1, ANERF_X6_IL>();
-#endif
+    group_schedule<6, 3, 1, X6_IL>();
 }
 
 __device__ __forceinline__ f32x16 mfma_x6(const float (&w)[16], const X6T& x, f32x16 c) {
@@ -373,12 +346,6 @@ __device__ __forceinline__ void mlp_layer_x6(f32x16 (&out)[RBO], f32x16 (&ain)[R
     // counted vmcnt waits exact (a conditional load makes the following waits drain to 0)
     const bool has_next = next != nullptr;
     auto prefetch = [&](int g) {
-#if ANERF_X6_PROBE == 1  // (diagnostic builds of tools/probe only: no weight loads)
-        return;
-#elif ANERF_X6_PROBE == 3  // (diagnostic: loads from a 4-group, L1-resident footprint)
-        load_group<12>(ring.v[(g + PD) % 4], rs, lane, (g + PD) % 4);
-        return;
-#endif
         if (g + PD < NG)
             load_group<12>(ring.v[(g + PD) % 4], rs, lane, g + PD);
         else if (NG % 4 == 0)
@@ -470,25 +437,9 @@ __device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float,
 // part rounds x to 11 significant bits in the f32 encoding (exact in fp16), the low part is the
 // exact remainder rounded to nearest even (v_cvt_pk_f16_f32), so x0 + x1 is within 2^-23 |x| of x
 // (a quarter of the values are not exact: the remainder can need 12 bits)
-#ifndef ANERF_SPLIT_MIX
-#define ANERF_SPLIT_MIX 1
-#endif
-#ifdef ANERF_H3_STAMPS  // (tools/probe/h4_probe.hip -DPROBE_STAMPS only: per-phase cycles of a layer, summed
-                        // into ANERF_H3_STAMPS[4] = preamble, lead groups, middle blocks, last block)
-#define ANERF_H3_HOOK(b)                                                       \
-    do {                                                                       \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
-        ph_acc[ph_cur] += now_ - ph_last;                                      \
-        ph_last = now_;                                                        \
-        ph_cur = (b);                                                          \
-    } while (0)
-#else
-#define ANERF_H3_HOOK(b) do { } while (0)
-#endif
 __device__ __forceinline__ void split2_pair(float a, float b, float t, H3T& T, int q) {
     typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     const float xa = a * t, xb = b * t;
-#if ANERF_SPLIT_MIX
     // (round 5) the high parts as one RNE conversion of the pair, the remainders x - x0 read the fp16 high
     // part straight from the packed pair by v_fma_mix_f32 (exact: x - x0 fits 13 bits), then one RNE
     // conversion: 4 instructions per pair where the integer rounding took 6
@@ -498,72 +449,25 @@ __device__ __forceinline__ void split2_pair(float a, float b, float t, H3T& T, i
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(lb) : "v"(hi), "v"(xb));
     T.d[0][q] = hi;
     T.d[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{la, lb}), f16x2));
-#else
-    const float ha = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, xa) + 0x1000u) & 0xffffe000u);
-    const float hb = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, xb) + 0x1000u) & 0xffffe000u);
-    T.d[0][q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ha, hb));
-    T.d[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{xa - ha, xb - hb}), f16x2));
-#endif
 }
 
-// fp16x4 with the x1 w1 product in fp8 (ANERF_F8_X1W1, round 5): the same split, and the low parts x1 also
-// as e4m3 bytes of the x1 w1 MFMA's B operand (x1 scaled by 2^8 into e4m3's range; the MFMA's block scale
-// 2^-8 undoes it): byte 2 (p & 1) .. +1 of dword `d` (two pairs per dword)
-#ifndef ANERF_F8_X1W1
-#define ANERF_F8_X1W1 0
-#endif
-// (round 6, experiment switch, off) the hidden layers' per-sample fp16 scale from a bound formed by the previous
-// layer (mlp_layer_h3): measured -0.6 % (1.2048 vs 1.2118 M rays/s, three alternating runs on one box, outputs
-// unchanged to 1e-8, profiles/r06i_ab_h3_bound.txt): the converts' maxima and 40 B/lane more scratch cost what
-// the drain before the scale saved
-#ifndef ANERF_H3_BOUND
-#define ANERF_H3_BOUND 0
-#endif
-template <bool HI_WORD>
-__device__ __forceinline__ void split2_pair_f8(float a, float b, float t, H3T& T, int q, unsigned& x8) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    const float xa = a * t, xb = b * t;
-    const unsigned hi = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{xa, xb}), f16x2));
-    float la, lb;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(la) : "v"(hi), "v"(xa));
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(lb) : "v"(hi), "v"(xb));
-    T.d[0][q] = hi;
-    T.d[1][q] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{la, lb}), f16x2));
-    x8 = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(la * 256.0f, lb * 256.0f, (int)x8, HI_WORD);
-}
-
-__device__ __forceinline__ void split2_block_pair_f8(const f32x16& hb, float t, H3T (&T)[2], int p,
-                                                     unsigned (&X8)[8], int half) {
-    const int s = p >> 2, q = p & 3;
-    if (p & 1)
-        split2_pair_f8<true>(hb[8 * s + 2 * q], hb[8 * s + 2 * q + 1], t, T[s], q, X8[4 * half + (p >> 1)]);
-    else
-        split2_pair_f8<false>(hb[8 * s + 2 * q], hb[8 * s + 2 * q + 1], t, T[s], q, X8[4 * half + (p >> 1)]);
-}
-
+// (removed experiments, code in 914abec: integer rounding of the high parts, -0.2 % / -1.5 %, profiles/
+// r05d_ab_split_mix.txt; fp16x4's x1 w1 product as one e4m3 MFMA, -2.4 %, r05k_ab_f8_ufuse.txt; the hidden layers'
+// scale from a bound formed by the previous layer, -0.6 %, r06i_ab_h3_bound.txt)
 __device__ __forceinline__ void split2_block_pair(const f32x16& hb, float t, H3T (&T)[2], int p) {
     const int s = p >> 2, q = p & 3;
-#if ANERF_X6_PROBE == 2  // (diagnostic builds of tools/probe only: no split arithmetic)
-    T[s].d[0][q] = T[s].d[1][q] = __builtin_bit_cast(unsigned, hb[8 * s + 2 * q]);
-    return;
-#endif
     split2_pair(hb[8 * s + 2 * q], hb[8 * s + 2 * q + 1], t, T[s], q);
 }
 
 // mlp_layer_h3's group: three MFMAs, the ring slot's four loads (even groups) after the first two
 // (NP = 3: fp16x3, NP = 4: fp16x4)
-#ifndef ANERF_H3_NLG  // (experiments: MFMAs followed by loads, loads after each; NLG x NL = 4)
-#define ANERF_H3_NLG 2
-#endif
-#ifndef ANERF_H3_LEAD_IL  // VALU per MFMA gap in the lead groups (input copies + bias initialisation; round 5
-                          // A/B: 4 +0.2 % over 2, 6 -0.2 %, profiles/r05e_ab.txt)
-#define ANERF_H3_LEAD_IL 4
-#endif
-template <int NP, int NV = ANERF_H3_IL>
+constexpr int H3_NLG = 2;  // (experiments: MFMAs followed by loads, loads after each; NLG x NL = 4)
+// VALU per MFMA gap in the lead groups (input copies + bias initialisation; round 5 A/B: 4 +0.2 % over 2, 6 -0.2 %,
+// profiles/r05e_ab.txt)
+constexpr int H3_LEAD_IL = 4;
+template <int NP, int NV = H3_IL>
 __device__ __forceinline__ void h3_group_schedule() {
-#if ANERF_H3_IL
-    group_schedule<NP, ANERF_H3_NLG, 4 / ANERF_H3_NLG, NV>();
-#endif
+    group_schedule<NP, H3_NLG, 4 / H3_NLG, NV>();
 }
 
 __device__ __forceinline__ f32x16 mfma_f16_32x32x16(f16x8 a, f16x8 b, f32x16 c) {
@@ -589,19 +493,6 @@ __device__ __forceinline__ f32x16 mfma_h3(const float (&w)[16], int half, const 
 // bit patterns, 0 for all-negative / zero inputs; NaN stays large) over this lane's and the partner
 // lane's values, scaled into [2^10, 2^11).  es: exponent of the units the input is in; on return the units of this layer's
 // output, es + shift + ew, kept within [-100, 60] so that bias * 2^es stays finite.
-// h3_scale_bits: the same from m, the bit pattern of a sample's largest relu'd input -- or of a bound on it (the
-// scaled maximum then lies at or below [2^10, 2^11): never above, the fp16 MFMA's range stays safe).
-__device__ __forceinline__ float h3_scale_bits(int m, int& es, int ew, int top, int cap = 60) {
-    int shift = m > 0 ? top - (m >> 23) : 0;  // (m >> 23: the biased exponent; top = 127 + 10)
-    // (cap: the skip layer's h part keeps its output units at most 2^cap, so that the fp16 x parts'
-    // features, scaled into those units, stay in range: enc16_units)
-    shift = max(shift, -100 - es - ew);
-    shift = min(shift, cap - es - ew);
-    shift = min(max(shift, -126), 126);
-    es += shift + ew;
-    return pow2f(shift);
-}
-
 template <int RBI>
 __device__ __forceinline__ float h3_scale(const f32x16 (&a)[RBI], int& es, int ew, int top, int cap = 60) {
     int m = 0;
@@ -615,35 +506,26 @@ __device__ __forceinline__ float h3_scale(const f32x16 (&a)[RBI], int& es, int e
             m = max(m, __builtin_bit_cast(int, v));
         }
     m = max(m, __shfl_xor(m, 32));
-    return h3_scale_bits(m, es, ew, top, cap);
+    int shift = m > 0 ? top - (m >> 23) : 0;  // (m >> 23: the biased exponent; top = 127 + 10)
+    // (cap: the skip layer's h part keeps its output units at most 2^cap, so that the fp16 x parts'
+    // features, scaled into those units, stay in range: enc16_units)
+    shift = max(shift, -100 - es - ew);
+    shift = min(shift, cap - es - ew);
+    shift = min(max(shift, -126), 126);
+    es += shift + ew;
+    return pow2f(shift);
 }
 
 // mlp_layer_x6's schedule with 8-float groups (3 MFMAs each), two groups per ring slot (slot
 // (g / 2) % 4, prefetched 3 slots = 6 groups ahead).  OUT_SAME layers alias out and ain; bias * 2^es
 // initialises the outputs.  ALPHA folds sig += w_alpha . h with h in the INPUT's units.
-// (round 6) Bound-based scale: with use_bnd the per-sample scale comes from *bnd, a bound on the sample's largest
-// relu'd input (bit pattern, in the input's units) that the PREVIOUS layer formed in the middle of its MFMAs,
-// instead of the maximum over all 128 inputs, which needed every MFMA of the previous layer to retire first
-// (h3_scale: the drain at each layer boundary).  A hidden layer (OUT_SAME, RBO == RBI) with rsum > 0 forms the
-// bound for the next: the true maximum M of its relu'd inputs (taken as its converts run, both lanes of the
-// sample) through |y_i| <= sum_k |W_ik| |x_k| + |b_i| <= rsum M + bmax (rsum, bmax: host constants of this
-// layer, real units), in the output's units and widened by 2^-10 for the fp32 rounding of its own arithmetic.
 template <int RBO, int RBI, bool OUT_SAME, bool ALPHA, int NP = 3>
 __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[RBI], f32x16 (&h)[RBI],
                                              const float* __restrict__ bias, const float* __restrict__ wp, int lane,
                                              Ring& ring, bool preloaded, const float* __restrict__ next,
                                              const float* __restrict__ wa, float& sig, int& es, int ew, int top,
-                                             int cap = 60, const float* __restrict__ w8 = nullptr, bool use_bnd = false,
-                                             int* bnd = nullptr, float rsum = -1.0f, float bmax = 0.0f) {
+                                             int cap = 60) {
     static_assert(RBO <= RBI, "h3 layer shape");
-    // F8: fp16x4 with x1 w1 as one v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3) per output block and pair of
-    // input blocks (64 k) instead of four f16 MFMAs: w8 holds the e4m3 w1 groups (pack_layer_f8)
-    constexpr bool F8 = (NP == 4) && ANERF_F8_X1W1 && (RBI % 2 == 0);
-    constexpr int NPG = F8 ? 3 : NP;  // f16 products per 16 k
-#ifdef ANERF_H3_STAMPS
-    unsigned long long ph_last = __builtin_amdgcn_s_memtime(), ph_acc[4] = {0, 0, 0, 0};
-    int ph_cur = 0;
-#endif
     constexpr int NG = 2 * RBO * RBI;
     constexpr int NS = NG / 2;  // ring slots of this layer
     constexpr int PS = 2;       // prefetch distance (slots)
@@ -651,24 +533,11 @@ __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[R
     const int hh = lane >> 5;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(wp);
     const __amdgpu_buffer_rsrc_t rn = make_rsrc(next ? next : wp);
-#if ANERF_X6_PROBE == 4  // (diagnostic builds of tools/probe only: no per-sample scale)
-    const float t = 1.0f;
-#else
-    const float t = use_bnd ? h3_scale_bits(*bnd, es, ew, top, cap) : h3_scale<RBI>(ain, es, ew, top, cap);
-#endif
+    const float t = h3_scale<RBI>(ain, es, ew, top, cap);
     const float S = pow2f(es);
-    constexpr bool MKB = OUT_SAME && RBO == RBI;  // (hidden layers: the true input maximum for the next bound)
-    int mx = 0;
     auto convert_half = [&](int rb, int half) {  // relu of 8 inputs (+ their 8 scaled bias outputs)
 #pragma unroll
         for (int i = 8 * half; i < 8 * half + 8; ++i) h[rb][i] = relu_act(ain[rb][i]);
-        if constexpr (MKB) {  // (integer maxima of the bit patterns, three operands each)
-#pragma unroll
-            for (int i = 8 * half; i < 8 * half + 8; i += 2) {
-                const float a = h[rb][i], b = h[rb][i + 1];
-                mx = max(mx, max(__builtin_bit_cast(int, a), __builtin_bit_cast(int, b)));
-            }
-        }
         if (OUT_SAME && rb < RBO) {
             const f32x4* p = reinterpret_cast<const f32x4*>(bias + (rb * 2 + hh) * 16 + 8 * half);
             const f32x4 v0 = p[0], v1 = p[1];
@@ -695,9 +564,6 @@ __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[R
     // last slot again without one: harmless; unconditional loads keep the counted vmcnt waits exact)
     const bool has_next = next != nullptr;
     auto prefetch = [&](int g) {
-#if ANERF_X6_PROBE == 1  // (diagnostic builds of tools/probe only: no weight loads)
-        return;
-#endif
         if (g & 1) return;
         const int G = g >> 1;
         if (G + PS < NS)
@@ -713,57 +579,24 @@ __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[R
     convert_half(0, 0);
     convert_half(0, 1);
     H3T T[2], Tn[2];
-    // (F8) e4m3 x1 of input blocks 2c, 2c + 1 in X8[c & 1] (block b: half b & 1); w1 groups in a 2-slot ring
-    unsigned X8[2][8];
-    float W8[2][16];
-    const __amdgpu_buffer_rsrc_t r8 = make_rsrc(w8 ? w8 : wp);
-    auto split_block_pair = [&](int b, int p, H3T (&TT)[2]) {
-        if constexpr (F8) split2_block_pair_f8(h[b], t, TT, p, X8[(b >> 1) & 1], b & 1);
-        else split2_block_pair(h[b], t, TT, p);
-    };
-    auto load8 = [&](int c, int o8) {  // w1 group (c, o8): output block o8, input blocks 2c, 2c + 1
-        if constexpr (F8) load_group<8>(W8[o8 & 1], r8, lane, c * RBO + o8);
-    };
-    auto mfma8 = [&](int c, int o8) {
-        if constexpr (F8) {
-            typedef int i32x8 __attribute__((ext_vector_type(8)));
-            typedef float f32x8 __attribute__((ext_vector_type(8)));
-            const float (&w)[16] = W8[o8 & 1];
-            const unsigned (&x)[8] = X8[c & 1];
-            const i32x8 a = __builtin_bit_cast(i32x8, (f32x8){w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]});
-            const i32x8 bx = i32x8{(int)x[0], (int)x[1], (int)x[2], (int)x[3], (int)x[4], (int)x[5], (int)x[6], (int)x[7]};
-            // (e4m3 both; block scales 2^-8 (E8M0 119) undo the 2^8 of the packed w1 and of x1)
-            out[o8] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bx, out[o8], 0, 0, 0, 119, 0, 119);
-        }
-    };
 #pragma unroll
-    for (int p = 0; p < 8; ++p) split_block_pair(0, p, T);
+    for (int p = 0; p < 8; ++p) split2_block_pair(h[0], t, T, p);
     constexpr int QL = NQ > 2 ? 2 : NQ;
 #pragma clang loop unroll(full)
     for (int g = 0; g < NQ; ++g) {
         __builtin_amdgcn_sched_barrier(0);
-        ANERF_H3_HOOK(1);
         prefetch(g);
-        if (F8 && g == NQ - 1) load8(0, 0);
         const int ob = g >> 1, s = g & 1;
-        out[ob] = mfma_h3<NPG>(ring.v[(g >> 1) % 4], g & 1, T[s], out[ob]);
+        out[ob] = mfma_h3<NP>(ring.v[(g >> 1) % 4], g & 1, T[s], out[ob]);
         if (ob == 0) alpha(0, s);
         if (ob + 1 < RBI && (ob + 1 < RBO || ob == 0)) convert_half(ob + 1, s);
         if (RBI > 1) {
 #pragma unroll
             for (int p = 0; p < 8; ++p)
                 if (pair_group(p, QL) == (g < QL ? -1 : g) || (g == NQ - 1 && pair_group(p, QL) > g))
-                    split_block_pair(1, p, Tn);
+                    split2_block_pair(h[1], t, Tn, p);
         }
-        h3_group_schedule<NPG, ANERF_H3_LEAD_IL>();
-    }
-    if constexpr (MKB) {  // every input converted: the next layer's bound, under this layer's MFMAs
-        if (bnd) {
-            mx = max(mx, __shfl_xor(mx, 32));
-            const float M = __builtin_bit_cast(float, mx) * t * pow2f(ew);  // (output units; powers of two: exact)
-            const float B = fmaf(rsum, M, bmax * S) * (1.0f + 0x1p-10f);
-            *bnd = rsum > 0.0f ? __builtin_bit_cast(int, B) : -1;
-        }
+        h3_group_schedule<NP, H3_LEAD_IL>();
     }
 #pragma clang loop unroll(full)
     for (int ib = 1; ib < RBI; ++ib) {
@@ -775,38 +608,21 @@ __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[R
         for (int q = 0; q < NQ; ++q) {
             const int s = q / RBO, ob = q % RBO;
             const int g = NQ + (ib - 1) * NQ + q;
-            // (F8) odd input blocks: the x1 w1 MFMA of output block q >> 1 in odd groups, its successor's
-            // w1 group loaded there; even blocks load the next pair's first group in their last group
-            const bool f8mm = F8 && (ib & 1) && (q & 1);
             __builtin_amdgcn_sched_barrier(0);
-            ANERF_H3_HOOK(ib + 1 < RBI ? 2 : 3);
             prefetch(g);
-            if (F8 && !(ib & 1) && q == NQ - 1) load8(ib / 2, 0);
-            out[ob] = mfma_h3<NPG>(ring.v[(g >> 1) % 4], g & 1, T[s], out[ob]);
-            if (f8mm) {
-                mfma8(ib / 2, q >> 1);
-                if ((q >> 1) + 1 < RBO) load8(ib / 2, (q >> 1) + 1);
-            }
+            out[ob] = mfma_h3<NP>(ring.v[(g >> 1) % 4], g & 1, T[s], out[ob]);
             if (ob == RBO - 1) alpha(ib, s);
             if (ib + 1 < RBI) {
                 if (conv_next && q < 2) convert_half(ib + 1, q);
 #pragma unroll
                 for (int p = 0; p < 8; ++p)
                     if (pair_group(p, q0) == q || (q == NQ - 1 && pair_group(p, q0) > q))
-                        split_block_pair(ib + 1, p, Tn);
+                        split2_block_pair(h[ib + 1], t, Tn, p);
             }
-            if (f8mm)
-                h3_group_schedule<NPG + 1>();
-            else
-                h3_group_schedule<NPG>();
+            h3_group_schedule<NP>();
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    ANERF_H3_HOOK(0);
-#ifdef ANERF_H3_STAMPS
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 4; ++i) atomicAdd(ANERF_H3_STAMPS + i, ph_acc[i]);
-#endif
 }
 
 // The MLP input x = [v (k*NJ + j), r (NJ*NV + 3j + c)] is split into two k-streams:
@@ -921,14 +737,9 @@ __device__ __forceinline__ JRow load_row(const float* __restrict__ sk, const flo
 // scheduled into.
 // With WV, also the joint's view-direction window w'_j = 1 - sigmoid(tau' (|q| - c'_j)) (hardware
 // sqrt/exp2/rcp, a few ulp; 0 for padding joints or without cutoff_viewdir) for the view layer.
-// (BC: -1 reads M.bone_cut in a uniform branch, 0 / 1 fix it at compile time, 2 selects — no branch inside
-// an MFMA region)
-template <bool WV, int BC = -1>
+template <bool WV>
 __device__ __forceinline__ void u_joint(const ModelDev& M, const JRow& r, bool valid, float px, float py, float pz,
                                         float& u0, float& u1, float& u2, bool& live, float& wv) {
-#ifdef ANERF_EXP_UFAST  // timing experiment only (stamps build): encoder VALU removed
-    u0 = px * r.a[0]; u1 = py; u2 = pz; live = false; wv = 0.0f; return;
-#endif
     float qx = fmaf(r.a[3], 1.0f, fmaf(r.a[2], pz, fmaf(r.a[1], py, r.a[0] * px)));
     float qy = fmaf(r.b[3], 1.0f, fmaf(r.b[2], pz, fmaf(r.b[1], py, r.b[0] * px)));
     float qz = fmaf(r.c[3], 1.0f, fmaf(r.c[2], pz, fmaf(r.c[1], py, r.c[0] * px)));
@@ -940,15 +751,7 @@ __device__ __forceinline__ void u_joint(const ModelDev& M, const JRow& r, bool v
     u0 = qx * inv;
     u1 = qy * inv;
     u2 = qz * inv;
-    if constexpr (BC == 2) {  // (the window as a select: both sides computed, no branch)
-        const float wb = 1.0f - __builtin_amdgcn_rcpf(
-                                    1.0f + __builtin_amdgcn_exp2f(-(M.tau_b * (__builtin_amdgcn_sqrtf(d2) - r.cb)) *
-                                                                  1.44269504f));
-        const float f = M.bone_cut ? wb : 1.0f;
-        u0 *= f;
-        u1 *= f;
-        u2 *= f;
-    } else if (BC > 0 || (BC < 0 && M.bone_cut)) {  // --cutoff_bones: u_j w_b (uniform branch), w_b = 1 - sigmoid(tau_b (|q| - c^b_j))
+    if (M.bone_cut) {  // --cutoff_bones: u_j w_b (uniform branch), w_b = 1 - sigmoid(tau_b (|q| - c^b_j))
         const float wb = 1.0f - __builtin_amdgcn_rcpf(
                                     1.0f + __builtin_amdgcn_exp2f(-(M.tau_b * (__builtin_amdgcn_sqrtf(d2) - r.cb)) *
                                                                   1.44269504f));
@@ -1090,9 +893,6 @@ __device__ __forceinline__ void u_part_lds(f32x16 (&acc)[RB], const ModelDev& M,
 }
 
 // ---- bf16x6 bone-direction parts (P == 2, layer 0 and the skip layer)
-#ifndef ANERF_UF_UNROLL
-#define ANERF_UF_UNROLL 2
-#endif
 // VALU pass: the 3 NJH2 bone-direction features of this lane (sample l & 31, joints h NJH2 ..
 // h NJH2 + NJH2 - 1) into the wave's LDS store as [q][64 lanes] (q = 3 p + c: conflict-free
 // b32 rows), the per-joint live ballots (JointMask) and the view windows w'_j — what u_part
@@ -1113,8 +913,8 @@ __device__ __forceinline__ void u_features_lds(const ModelDev& M, const float* _
         m0 |= (jb < 64 ? hi : 0ull) << (jb & 63);
         m1 |= (jb >= 64 ? hi : 0ull) << (jb & 63);
     };
-    // (U joints per iteration: the chains of U joints interleave; round 5: U = 4, was 2)
-    constexpr int U = ANERF_UF_UNROLL;
+    // (U joints per iteration: the chains of U joints interleave; 4 / 6: -1.1 % / -6.5 %, profiles/r05f_ab.txt)
+    constexpr int U = 2;
     JRow r[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) r[k] = load_row(sk, cut, j0 + min(k, njh2 - 1), nj, M.bone_cut != 0);
@@ -1178,9 +978,6 @@ __device__ __forceinline__ int block_live_count(const ModelDev& M, const float* 
     return cnt;
 }
 
-#ifndef ANERF_X6_BARRIERS
-#define ANERF_X6_BARRIERS 3
-#endif
 // Precision modes whose four waves run the hidden layers in lock step (a workgroup barrier before
 // each, blocks in live-joint order): the split modes bf16x6, fp16x4 and fp16x3 (+2.6 % fp16x4,
 // +0.8 % fp16x3, bit-identical outputs: profiles/r04i_ab_fp16x4.txt, r04y_ab_h3lock.txt)
@@ -1273,7 +1070,7 @@ __device__ __forceinline__ void v_part(f32x16 (&acc)[RB], const ModelDev& M, con
 #pragma unroll
     for (int g = 0; g < 2; ++g)
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) ring[g][rb] = bload2_v(rs, voff, ((j * GB + g) * RB + rb) * 512);
+        for (int rb = 0; rb < RB; ++rb) ring[g][rb] = bload2(rs, voff, ((j * GB + g) * RB + rb) * 512);
     float f[KB];
     {
         float dist, w, u, uf;
@@ -1302,11 +1099,11 @@ __device__ __forceinline__ void v_part(f32x16 (&acc)[RB], const ModelDev& M, con
             if (g + PD < GB) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
-                    ring[(g + PD) % GB][rb] = bload2_v(rs, voff, ((j * GB + g + PD) * RB + rb) * 512);
+                    ring[(g + PD) % GB][rb] = bload2(rs, voff, ((j * GB + g + PD) * RB + rb) * 512);
             } else {  // the next joint's first groups (this joint's again after the last: harmless)
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb)
-                    ring[(g + PD) % GB][rb] = bload2_v(rs, voff, ((jg * GB + g + PD - GB) * RB + rb) * 512);
+                    ring[(g + PD) % GB][rb] = bload2(rs, voff, ((jg * GB + g + PD - GB) * RB + rb) * 512);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -1486,109 +1283,8 @@ __device__ __forceinline__ void u_part_h(f32x16 (&acc)[RB], const ModelDev& M, c
     }
 }
 
-// (round 5, ANERF_UFUSE) layer 0's fp16 bone-direction part with u_features_lds's VALU pass under its MFMAs:
-// k-step s (8 features) runs while joints 3 s + 3 .. 3 s + 5 are computed, one per two-group scheduling
-// region, and the features of k-step s + 1 (joints <= 3 s + 5) are read back and split in the last two
-// regions.  The features still go through the LDS store (the skip layer reads them again; LDS is in order
-// within a wave).  Joints past NJH2 - 1 recompute the last one (identical stores and ballots: no branch).
-// --cutoff_bones' window is a select (a uniform branch would split the MFMA regions).
-#ifndef ANERF_UFUSE
-#define ANERF_UFUSE 0
-#endif
-#ifndef ANERF_UFUSE_PF  // (the next joint's skeleton row loaded one region ahead)
-#define ANERF_UFUSE_PF 1
-#endif
-#ifndef ANERF_UFUSE_IL
-#define ANERF_UFUSE_IL 1
-#endif
-#ifndef ANERF_UFUSE_BC  // (2: --cutoff_bones' window as a select; 0: the caller takes the unfused path with it)
-#define ANERF_UFUSE_BC 2
-#endif
-template <int RB, int NP, bool WV>
-__device__ __forceinline__ void u_part_h_fused(f32x16 (&acc)[RB], const ModelDev& M, const float* __restrict__ wp,
-                                               const float* __restrict__ sk, const float* __restrict__ cut, float px,
-                                               float py, float pz, int lane, JointMask* mask, float* __restrict__ uf,
-                                               float* __restrict__ wvo, Ring& ring, float t) {
-    static_assert(RB == 8, "u_part_h_fused: eight groups per k-step (three joint regions + the split region)");
-    constexpr int PD = 3, NV = NP == 4 ? 8 : 10;
-    const int hh = lane >> 5, njh2 = M.njh2, nj = M.nj, j0 = hh * njh2;
-    const int nq = 3 * njh2, ns = (nq + 7) / 8, ng = ns * RB;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(wp);
-    uint64_t m0 = 0, m1 = 0;
-    const bool bc = M.bone_cut != 0;
-    auto row = [&](int p) {  // (load_row with the bone window's column selected by address: no branch)
-        const int j = j0 + min(p, njh2 - 1), jc = j < nj ? j : 0;
-        const f32x4* q = reinterpret_cast<const f32x4*>(sk + 12 * jc);
-        return JRow{q[0], q[1], q[2], cut[2 * nj + jc], cut[nj + jc], cut[(bc ? 3 : 2) * nj + jc]};
-    };
-    auto joint = [&](int p, const JRow& r) {
-        const int pc = min(p, njh2 - 1);
-        float u0, u1, u2, wv;
-        bool live;
-        u_joint<WV, ANERF_UFUSE_BC>(M, r, j0 + pc < nj, px, py, pz, u0, u1, u2, live, wv);
-        uf[(3 * pc + 0) * 64 + lane] = u0;
-        uf[(3 * pc + 1) * 64 + lane] = u1;
-        uf[(3 * pc + 2) * 64 + lane] = u2;
-        if constexpr (WV) wvo[pc * 64 + lane] = wv;
-        const uint64_t b = __ballot(live);  // (as u_features_lds: joint pc, half 1 joint pc + njh2)
-        const uint64_t lo = (b & 0xffffffffull) ? 1ull : 0ull, hi = (b >> 32) ? 1ull : 0ull;
-        const int jb = pc + njh2;
-        m0 |= lo << pc;
-        m0 |= (jb < 64 ? hi : 0ull) << (jb & 63);
-        m1 |= (jb >= 64 ? hi : 0ull) << (jb & 63);
-    };
-    auto feat = [&](int q) { return mask_f(uf[min(q, nq - 1) * 64 + lane], q < nq); };
-    {
-        const JRow r0 = row(0), r1 = row(1), r2 = row(2);
-        joint(0, r0);
-        joint(1, r1);
-        joint(2, r2);
-    }
-#if ANERF_UFUSE_PF
-    JRow rn = row(3);
-#endif
-    H3T cur, nxt;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) split2_pair(feat(2 * e), feat(2 * e + 1), t, cur, e);
-    for (int s = 0; s < ns; ++s) {
-        float fn[8];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            const int g = s * RB + rb;
-            if (rb % 2 == 0) __builtin_amdgcn_sched_barrier(0);
-            load_group<8>(ring.v[(rb + PD) % 4], rs, lane, min(g + PD, ng - 1));
-            acc[rb] = mfma_h3<NP>(ring.v[rb % 4], 0, cur, acc[rb]);
-            if (rb == 0 || rb == 2 || rb == 4) {
-                const int p = 3 * s + 3 + rb / 2;
-#if ANERF_UFUSE_PF
-                const JRow r = rn;
-                rn = row(p + 1);
-                joint(p, r);
-#else
-                joint(p, row(p));
-#endif
-            }
-            if (rb == 5) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fn[j] = feat(8 * (s + 1) + j);
-            }
-            if (rb >= 6) {
-                const int e = 2 * (rb - 6);
-                split2_pair(fn[2 * e], fn[2 * e + 1], t, nxt, e);
-                split2_pair(fn[2 * e + 2], fn[2 * e + 3], t, nxt, e + 1);
-            }
-#if ANERF_UFUSE_IL
-            if (rb % 2 == 1) interleave_mfma_valu<2 * NP, NV>();
-#endif
-        }
-        cur = nxt;
-    }
-    if (mask) {
-        mask->m0 = m0;
-        mask->m1 = m1;
-    }
-}
-
+// (removed experiment, code in 914abec: layer 0's fp16 bone-direction part with u_features_lds's VALU pass fused
+// under its MFMAs, -0.5 %, profiles/r05k_ab_f8_ufuse.txt)
 template <int RB, int MR, int NP>
 __device__ __forceinline__ void v_part_h(f32x16 (&acc)[RB], const ModelDev& M, const float* __restrict__ wp,
                                          const float* __restrict__ sk, const float* __restrict__ cut, float px,
@@ -1722,7 +1418,7 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
                                           const float* __restrict__ bias, float* __restrict__ uf,
                                           float* __restrict__ wvo, f32x16 (&acc)[W / 32], f32x16 (&h)[W / 32],
                                           Ring& ring, JointMask& mask, const float* __restrict__ after_last,
-                                          Stamps& st, int& es, int* bnd = nullptr, bool* have_bnd = nullptr) {
+                                          Stamps& st, int& es) {
     constexpr int RB = W / 32;
     const int hh = lane >> 5;
     float nosig = 0.0f;
@@ -1730,7 +1426,7 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
     constexpr bool HANDOFF = (2 * RB == 16);  // u-part groups have the regs layers' group size
     // bf16x6 / fp16x3 with the LDS feature store: features in a VALU pass, both bone-direction parts as x6
     constexpr bool UX6 = (P >= 2) && (RB % 4 == 0);
-    const bool ux6 = UX6 && M.ux6 && uf != nullptr;
+    const bool ux6 = UX6 && uf != nullptr;
     // fp16x4 / fp16x3 with bounded windowed features: the encoder-fed parts as fp16 splits (NP products),
     // in units 2^enc_e0 (layer 0) and below 2^enc_cap (the skip layer), enc16_units
     constexpr bool H16 = (P >= 3) && UX6;
@@ -1748,14 +1444,9 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
     if (enc16) {
         if constexpr (H16) u_part_h_preload<RB>(net.wuh[0], lane, ring);  // (latency under the VALU pass)
         const float t0 = pow2f(net.enc_e0 - net.ewh_u[0]);
-        if (ANERF_UFUSE && RB == 8 && (ANERF_UFUSE_BC == 2 || !M.bone_cut)) {
-            if constexpr (H16 && RB == 8)
-                u_part_h_fused<RB, NPH, WV>(acc, M, net.wuh[0], sk, cut, px, py, pz, lane, &mask, uf, wvo, ring, t0);
-        } else {
-            u_features_lds<WV>(M, sk, cut, px, py, pz, lane, &mask, uf, wvo);
-            STAMP(st, 14);
-            if constexpr (H16) u_part_h<RB, NPH>(acc, M, net.wuh[0], uf, lane, ring, true, t0);
-        }
+        u_features_lds<WV>(M, sk, cut, px, py, pz, lane, &mask, uf, wvo);
+        STAMP(st, 14);
+        if constexpr (H16) u_part_h<RB, NPH>(acc, M, net.wuh[0], uf, lane, ring, true, t0);
     } else if (ux6) {
         if constexpr (UX6) u_part_x6_preload<RB>(net.wu6, lane, ring);  // (latency under the VALU pass)
         u_features_lds<WV>(M, sk, cut, px, py, pz, lane, &mask, uf, wvo);
@@ -1781,9 +1472,6 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
     }
     STAMP(st, 9);
     bool pre6 = false;
-    // fp16 modes (ANERF_H3_BOUND): layer L >= 2 takes its scale from the bound layer L - 1 formed, unless L - 1 is the
-    // skip layer (its x parts join the output after the h part; their features have no bound here)
-    bool hb = false;
     for (int L = 1; L < M.D; ++L) {
         const float* after = L + 1 < M.D ? wl[L + 1] : after_last;
         const bool skl = (L == M.skip + 1);
@@ -1793,26 +1481,19 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
         // CU per group otherwise, and the waves drift apart over the windowed parts' live joints.
         // +2.1 % (A/B, profiles/r03_ab_experiments.txt); the calling block loop must have the same
         // trip count on every wave (SYNC: the render and density kernels' block loops).
-        // (ANERF_X6_BARRIERS, experiments: 3 before every hidden layer, 2 before layer 1 and the layer
-        // after the skip layer, 1 before layer 1 only, 0 none)
-        constexpr int XB = ANERF_X6_BARRIERS;
-        if constexpr (SYNC && lockstep_mode<P>() && XB > 0) {
-            if (XB == 3 || L == 1 || (XB == 2 && L == M.skip + 2)) {
-                __builtin_amdgcn_s_barrier();
-                STAMP(st, 18);  // (stamps build: the wait at this barrier)
-            }
+        // (barriers before layer 1 and after the skip layer only, or before layer 1 only: within 0.2 %,
+        // profiles/r04s_barriers_ab.txt, r05v_ab_schedule_knobs.txt)
+        if constexpr (SYNC && lockstep_mode<P>()) {
+            __builtin_amdgcn_s_barrier();
+            STAMP(st, 18);  // (stamps build: the wait at this barrier)
         }
         if constexpr (P >= 3) {
             // the next h3 phase (the next hidden layer or the view layer) is prefetched; not across the
             // skip layer's x parts, which load themselves and scale their B operands by 2^es (the
             // units the h part left in the accumulators)
             const float* nxth = skl ? nullptr : after;
-            const bool use = ANERF_H3_BOUND && bnd && hb;
             mlp_layer_h3<RB, RB, true, false, P == 4 ? 4 : 3>(acc, acc, h, bias + L * W, wl[L], lane, ring, pre6, nxth, nullptr,
-                                              nosig, es, net.ewl[L], M.h3_top, (skl && enc16) ? net.enc_cap : 60,
-                                              net.wl8[L], use, ANERF_H3_BOUND ? bnd : nullptr,
-                                              skl ? -1.0f : net.hrsum[L], net.hbmax[L]);
-            hb = !skl;
+                                              nosig, es, net.ewl[L], M.h3_top, (skl && enc16) ? net.enc_cap : 60);
             pre6 = nxth != nullptr;
             if (skl) {  // the f32 skip x parts take their first groups from the ring (the x6 one loads itself)
                 if (!ux6) ring_preload<2 * RB>(ring, net.wskipu, lane);
@@ -1822,7 +1503,7 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
             // the next x6 phase: the next layer, after_last, or the skip layer's x6 bone-direction part
             // (selected by uniform values only: uf is a per-wave LDS pointer, derived from threadIdx,
             // and a pointer selected by it becomes a VGPR whose buffer loads waterfall)
-            const float* nxt6 = skl ? ((UX6 && M.ux6) ? net.wskipu6 : nullptr) : after;
+            const float* nxt6 = skl ? (UX6 ? net.wskipu6 : nullptr) : after;
             mlp_layer_x6<RB, RB, true, false>(acc, acc, h, bias + L * W, wl[L], lane, ring, pre6, nxt6, nullptr,
                                               nosig);
             pre6 = nxt6 != nullptr && !skl;  // (the skip x part consumes its preloaded groups itself)
@@ -1862,7 +1543,6 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
             STAMP(st, 12);
         }
     }
-    if (have_bnd) *have_bnd = ANERF_H3_BOUND && bnd && hb && M.D > 1;
     return pre6;  // (bf16x6 / fp16x3: after_last's first groups are in the ring)
 }
 
@@ -1889,11 +1569,8 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
     JointMask mask;
     Ring ring;
     int es = 0;
-    int bnd = -1;
-    bool have_bnd = false;
     const bool pre = mlp_trunk<W, MR, true, P>(M, net, sk, cut, px, py, pz, lane, bias, uf, wvp, acc, h, ring, mask,
-                                               P >= 3 ? net.wviewh : (P == 2 ? net.wview6 : net.wview), st, es,
-                                               P >= 3 ? &bnd : nullptr, &have_bnd);
+                                               P >= 3 ? net.wviewh : (P == 2 ? net.wview6 : net.wview), st, es);
     // views_linears.0 with feature_linear fused in (W' = Wv_f Wf, see pack_net) on relu(h_last),
     // alpha_linear folded into its groups (same relu'd B operands), + the factorised
     // direction / code / bias part from G, then relu
@@ -1902,8 +1579,7 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
     if constexpr (P >= 3) {
         const int es_h = es;  // the alpha head sums the last hidden layer's activations, in its units
         mlp_layer_h3<RBV, RB, false, true, P == 4 ? 4 : 3>(av, acc, h, nullptr, net.wviewh, lane, ring, pre, nullptr,
-                                           bias + (M.D + 1) * W, sig, es, net.ew_view, M.h3_top, 60, net.wview8,
-                                           have_bnd, &bnd);
+                                           bias + (M.D + 1) * W, sig, es, net.ew_view, M.h3_top);
         sig *= pow2f(-es_h);
     } else if constexpr (P == 2)
         mlp_layer_x6<RBV, RB, false, true>(av, acc, h, nullptr, net.wview6, lane, ring, pre, nullptr,
@@ -1933,7 +1609,7 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
     STAMP(st, 13);
     if (mfma_count && lane == 0) {  // exact MFMA work of this block (wave-uniform quantities)
         const int act = __builtin_popcountll(mask.m0) + __builtin_popcountll(mask.m1);
-        const bool ux6 = (P >= 2) && (RB % 4 == 0) && uf != nullptr && M.ux6;  // as in mlp_trunk
+        const bool ux6 = (P >= 2) && (RB % 4 == 0) && uf != nullptr;  // as in mlp_trunk
         constexpr bool vx6 = (P >= 2) && (RB % 4 == 0);
         const int npe = (P >= 3 && ux6 && M.enc16) ? (P == 4 ? 4 : 3) : 6;  // products of the encoder-fed parts
         const int xk = (ux6 ? 0 : 3 * M.njh2) + (vx6 ? 0 : act * VPart<MR>::KB);  // f32 k-steps of one x part

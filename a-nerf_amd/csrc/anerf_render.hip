@@ -53,11 +53,8 @@ using namespace anerf;
 #include "anerf_batch.hpp"
 #include "anerf_pack.hpp"
 
-// Experiment switches are compile-time only (tools/build_ab.sh -D...): the shipped library reads no
-// environment variable that could change its numerics or schedule.
-#ifndef ANERF_UX6
-#define ANERF_UX6 1  // split-precision bone-direction parts; 0: f32 MFMA (A/B builds only)
-#endif
+// The shipped library reads no environment variable that could change its numerics or schedule: experiments
+// are built from a patched copy of the sources (tools/build_ab.sh).
 
 int anerf_internal_fail(int code, const char* msg) { return fail(code, msg); }  // for anerf_gemm.hip
 
@@ -201,7 +198,6 @@ int anerf_model_create(const anerf_model_desc* desc, const anerf_net_weights* co
     md.cfc = desc->framecode_ch;
     md.n_codes = desc->n_framecodes;
     md.softplus = desc->density_softplus;
-    md.ux6 = ANERF_UX6;  // split bone-direction parts (u_part_x6); 0 only in experiment builds (tools/build_ab.sh)
     md.single_net = desc->single_net ? 1 : 0;
     // (both transforms live in the CutoffEmbedder: without use_cutoff the kp embedder is plain)
     md.cut_to = desc->use_cutoff && (desc->encoder_flags & ANERF_ENC_CUT_TO_DIST) ? 1 : 0;
@@ -326,13 +322,6 @@ int anerf_near_far(const float* ray_batch, int32_t ray_stride, int64_t n_rays, c
     return ANERF_OK;
 }
 
-// -DANERF_FUSED_PASSES=1 (experiment builds of tools/build_ab.sh only): both passes in one launch, the
-// round-1 schedule kept for A/B measurements
-#ifndef ANERF_FUSED_PASSES
-#define ANERF_FUSED_PASSES 0
-#endif
-static constexpr bool fused_passes() { return ANERF_FUSED_PASSES != 0; }
-
 int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_stride, int64_t n_rays,
                       const float* skts, const float* cyls, int32_t n_poses, const int32_t* ray_pose,
                       const float* cams, int32_t n_samples, int32_t n_importance, int32_t chunk, int32_t precision,
@@ -433,18 +422,16 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
     // With importance sampling the coarse and the fine pass run as two launches: every CU then
     // streams one network's weights at a time, which fit an XCD's 4 MB L2 (both together do not);
     // the fine z lists (T floats per ray) go through the workspace.
-    // (single_net: one network, so one launch; the fine pass reuses the coarse raws, biases and G in LDS)
-    const int pstep = (I > 0 && !fused_passes() && !m->desc.single_net) ? 1 : 2;
+    // (single_net: one network, so one launch; the fine pass reuses the coarse raws, biases and G in LDS.  Both passes
+    // of two networks in one launch, the round-1 schedule: removed, code in 914abec)
+    const int pstep = (I > 0 && !m->desc.single_net) ? 1 : 2;
     a.zf_ws = I > 0 ? reinterpret_cast<float*>((char*)workspace + ws_near_far_bytes(n_rays)) : nullptr;
     unsigned grid = (unsigned)((n_rays + R - 1) / R);
     unsigned* queues = reinterpret_cast<unsigned*>((char*)workspace + ws_near_far_bytes(n_rays) +
                                                    ws_zf_bytes(n_rays, S, I));
-    int ncu = 256;  // ANERF_PERSIST: as many workgroups as fit on the chip at once, items from the band queues
-    if (ANERF_PERSIST) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        HIP_TRY(hipMemsetAsync(queues, 0, 2 * 8 * sizeof(unsigned), st));
-    }
+    int ncu = 256;  // persistent workgroups: as many as fit on the chip at once, items from the band queues
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    HIP_TRY(hipMemsetAsync(queues, 0, 2 * 8 * sizeof(unsigned), st));
     const size_t lds_bytes = (size_t)P.total * 4;
     const int mr = layout_multires(m->desc.multires);  // (the instance; smaller counts zero-padded, anerf_pack.hpp)
 #define ANERF_LAUNCH(WW, MM)                                                                         \
@@ -455,13 +442,10 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
                  : precision == ANERF_PREC_FP16X4 ? render_kernel<WW, MM, 4> : render_kernel<WW, MM, 0>; \
         HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                     (int)lds_bytes));                                               \
-        unsigned g = grid;                                                                          \
-        if (ANERF_PERSIST) {                                                                        \
-            int nb = 1;                                                                             \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 256, lds_bytes) != hipSuccess || nb < 1) \
-                nb = 1;                                                                             \
-            g = std::min<unsigned>(grid, (unsigned)(ncu * nb));                                     \
-        }                                                                                           \
+        int nb = 1;                                                                                 \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 256, lds_bytes) != hipSuccess || nb < 1) \
+            nb = 1;                                                                                 \
+        const unsigned g = std::min<unsigned>(grid, (unsigned)(ncu * nb));                          \
         for (int p0 = 0; p0 < 2; p0 += pstep) {                                                     \
             a.pass0 = p0;                                                                           \
             a.pass1 = p0 + pstep;                                                                   \

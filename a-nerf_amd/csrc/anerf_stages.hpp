@@ -96,7 +96,7 @@ __device__ void compute_view_factor(const ModelDev& M, const NetDev& net, float*
         auto load_col = [&](float (&dst)[TP], int col) {
 #pragma unroll
             for (int q = 0; q < TP / 4; ++q) {
-                const f32x4 x = bload4_g(rs, (col * WH + nn) * TP * 4 + q * 16, 0);
+                const f32x4 x = bload4(rs, (col * WH + nn) * TP * 4 + q * 16, 0);
                 dst[4 * q] = x[0], dst[4 * q + 1] = x[1], dst[4 * q + 2] = x[2], dst[4 * q + 3] = x[3];
             }
         };

@@ -880,10 +880,7 @@ __global__ __launch_bounds__(256) void train_view_mix_backward_kernel(const floa
 // normalised (raw under --view_type world), T = [e, sin 2^m e, cos 2^m e ...] (slot f component c at k = 3 f + c),
 // Wv' the view layer's view columns (column f 3 NJ + 3 j + c) times the --freq_schedule weights.  One joint per
 // workgroup (its Wv' slice staged in LDS).
-#ifndef ANERF_VF_RAYS_B
-#define ANERF_VF_RAYS_B 128
-#endif
-constexpr int VF_RC = 64, VF_RAYS_B = ANERF_VF_RAYS_B, VF_KG = 4;  // (rays per chunk / per backward workgroup; float4
+constexpr int VF_RC = 64, VF_RAYS_B = 128, VF_KG = 4;                // (rays per chunk / per backward workgroup; float4
                                                                    // dL/dWv groups per thread)
 __device__ __forceinline__ bool view_terms(const ModelDev& M, const float* __restrict__ rb, int stride, int64_t r,
                                            const float* __restrict__ skts, const int32_t* __restrict__ ray_pose,

@@ -257,13 +257,8 @@ __global__ __launch_bounds__(256, 1) void train_mlp_fwd_kernel(TfArgs A) {
     for (long long blk = (long long)blockIdx.x * 4 + wave; blk < nblk; blk += nw) {
         const long long row0 = blk * 32;
         const int rows = (int)min((long long)32, A.M - row0);
-#ifdef ANERF_TF_XL2  // (diagnostic A/B only: every wave reads feature rows 0..63, L2-resident)
-        const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(A.feat + (blk & 1) * 32 * A.ldf), 0, (int)(rows * A.ldf * 4), 0x00020000);
-#else
         const __amdgpu_buffer_rsrc_t rf =
             __builtin_amdgcn_make_buffer_rsrc((void*)(A.feat + row0 * A.ldf), 0, (int)(rows * A.ldf * 4), 0x00020000);
-#endif
         Ring ring;
         f32x16 acc[RB], h[RB];
         float nosig = 0.0f;

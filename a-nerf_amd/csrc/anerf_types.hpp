@@ -68,16 +68,11 @@ struct NetDev {
     const float* wlh[MAXL];  // [i>0] activation parts as fp16x3 fragments (pack_layer_h3), scaled by 2^ewl[i]
     const float* wviewh;     // wview as fp16x3 fragments, scaled by 2^ew_view
     int ewl[MAXL], ew_view;
-    // (round 6) per hidden layer (h part only): max_i sum_k |W_ik| and max_i |b_i| (real units, rounded up), the
-    // next layer's scale bound (mlp_layer_h3)
-    float hrsum[MAXL], hbmax[MAXL];
     // fp16 encoder-fed parts (ModelDev::enc16): [0] layer 0, [1] the skip layer (null without one); the
     // bone-direction (u) and windowed (v) weights scaled by 2^ewh_u / 2^ewh_v (pack_upart_h, pack_vpart_h)
     const float* wuh[2];
     const float* wvh[2];
     int ewh_u[2], ewh_v[2];
-    const float* wl8[MAXL];  // [i>0] fp16x4's x1 w1 products: the e4m3 w1 of the fp16 planes (pack_layer_f8)
-    const float* wview8;     // the same for wviewh
     int enc_e0;   // exponent of layer 0's accumulator units (enc16)
     int enc_cap;  // the largest exponent of the skip layer's accumulator units its x parts' features allow
     float balpha;
@@ -86,7 +81,6 @@ struct NetDev {
 struct ModelDev {
     int nj, njh2, ngh, D, skip, mr, mrv, use_cutoff, cutoff_inputs, cutoff_viewdir, cfc, n_codes, softplus;
     int sparse;  // windowed features are exactly 0 where w == 0 (use_cutoff && cutoff_inputs)
-    int ux6;     // bf16x6: bone-direction parts as x6 from the LDS feature store (u_part_x6)
     int single_net;  // one network for both passes; the fine pass evaluates only the I new samples
     int cut_to, shift_in;  // kp encoder input transforms (ANERF_ENC_CUT_TO_DIST / _CUTOFF_SHIFT)
     int h3_top;      // fp16x3: biased exponent the largest scaled activation of a sample gets (127 + 10)
@@ -125,7 +119,7 @@ struct RenderArgs {
     int pass0, pass1;  // passes [pass0, pass1) of this launch (0 coarse, 1 fine)
     float* zf_ws;      // n x T: the fine pass's sorted z, handed from the coarse launch to the fine one
     int lindisp;       // sample_from_lineseg in inverse depth (ANERF_FLAG_LINDISP)
-    unsigned* queue;   // ANERF_PERSIST: this launch's 8 band counters (workspace, zeroed before the launch)
+    unsigned* queue;   // this launch's 8 band counters (persistent workgroups) (workspace, zeroed before the launch)
 };
 
 // ======================================================================= LDS plan

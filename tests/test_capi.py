@@ -78,6 +78,21 @@ def test_library_reads_no_experiment_switches_from_the_environment():
         assert name not in blob, name
 
 
+def test_compile_time_switches_are_the_declared_ones():
+    """Every ANERF_* macro that a preprocessor conditional of the kernel sources tests is declared here:
+    the switches of the maintained diagnostic and A/B tools (DESIGN.md lists the tool each serves).
+    Experiment scaffolding does not stay in the product sources: build it from a patched copy."""
+    allowed = {"ANERF_STAMPS", "ANERF_ASM_MARKS", "ANERF_AB_FAST", "ANERF_H3_TARGET"}
+    csrc = os.path.join(REPO, "a-nerf_amd", "csrc")
+    found = set()
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as f:
+            src = f.read().replace("\\\n", " ")
+        for cond in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", src, flags=re.M):
+            found |= set(re.findall(r"\bANERF_[A-Z0-9_]+", cond))
+    assert found == allowed, sorted(found ^ allowed)
+
+
 def test_build_discards_a_library_whose_sources_moved(tmp_path, monkeypatch):
     """build.py keeps only a build whose sources did not change while hipcc ran (a header edited between
     the offload passes gives host and device different struct layouts) and renames it into place whole."""
