@@ -5,9 +5,9 @@ include/anerf.h is stored next to the library (`libanerf_hip.so.stamp`).  A ship
 stamp does not match the sources is rebuilt, never reused because of its mtime.
 
 The translation units compile in parallel into objects cached under `.objs/` by the hash of
-their own dependencies (anerf_gemm.hip reads only include/anerf.h, anerf_iso.hip its case table and
-include/anerf.h), then link into the library: an edit of the training GEMMs or of the iso-surface
-kernels recompiles one unit, not the render kernels' instances.
+their own dependencies (anerf_gemm.hip and anerf_mesh.hip read only include/anerf.h, anerf_iso.hip its case
+table and include/anerf.h), then link into the library: an edit of the training GEMMs, of the iso-surface or
+of the mesh kernels recompiles one unit, not the render kernels' instances.
 """
 import hashlib
 import os
@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "anerf.h")
 SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_gemm.hip"),
-       os.path.join(CSRC, "anerf_iso.hip")]
+       os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip")]
 OUT = os.path.join(HERE, "libanerf_hip.so")
 STAMP = OUT + ".stamp"
 OBJS = os.path.join(HERE, ".objs")
@@ -48,9 +48,9 @@ def source_hash():
 
 
 def unit_deps(src):
-    """The files a translation unit reads: anerf_gemm.hip only the C header, anerf_iso.hip its case table and the
-    C header, anerf_render.hip every csrc header."""
-    if os.path.basename(src) == "anerf_gemm.hip":
+    """The files a translation unit reads: anerf_gemm.hip and anerf_mesh.hip only the C header, anerf_iso.hip its
+    case table and the C header, anerf_render.hip every csrc header."""
+    if os.path.basename(src) in ("anerf_gemm.hip", "anerf_mesh.hip"):
         return [src, HEADER]
     if os.path.basename(src) == "anerf_iso.hip":
         return [src, os.path.join(CSRC, "anerf_iso_table.inc"), HEADER]

@@ -290,7 +290,7 @@ def read_ply(path, attributes=False):
 
 
 def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False, normals=False, colors=False,
-                   view="normal", cams=None, radiance=None):
+                   view="normal", cams=None, radiance=None, keep_largest=None, min_triangles=0):
     """extract_mesh's second half: the iso-surface of a caster's render_mesh_density grid (relu on load, as
     run_render.render_mesh's np.maximum(raw_d, 0)) in the requested coordinates:
       "index"  array-index coordinates, as mcubes.marching_cubes;
@@ -305,7 +305,11 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
                  a pose) returns at the WORLD vertices, whatever `coords`, in [0, 1].  view="normal": each vertex
                  is looked at along its inward world normal (from outside, straight on), and where the normal is
                  zero along the direction from the vertex to kps[0, 0]; view=(x, y, z): one direction for all.
-    An empty mesh gives (0, 3) attributes and launches nothing more."""
+    An empty mesh gives (0, 3) attributes and launches nothing more.
+    `keep_largest` / `min_triangles` drop connected components (meshops.filter_mesh: keep_largest=1 keeps the body
+    and drops the floaters and cavity surfaces of a noisy density) right after the extraction, before the colour
+    query: dropped vertices cost no radiance work, and the normals returned are the kept rows.  With the defaults
+    that code is not entered."""
     if coords not in ("unit", "index", "world"):
         raise ValueError(f"coords must be 'unit', 'index' or 'world', got {coords!r}")
     one_dir = None
@@ -323,6 +327,12 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     else:
         v, t = isosurface(grid, threshold, relu=True, flip=wflip)
         n = None
+    if keep_largest is not None or min_triangles > 0:
+        from .meshops import filter_mesh
+        if n is None:
+            v, t = filter_mesh(v, t, keep_largest=keep_largest, min_triangles=min_triangles)
+        else:
+            v, t, (n,) = filter_mesh(v, t, [n], keep_largest=keep_largest, min_triangles=min_triangles)
     vi = v
     if coords == "unit":
         v = v / res - .5
@@ -355,20 +365,23 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
 
 @torch.no_grad()
 def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, res=255, threshold=10.,
-                normals=False, colors=False, view="normal"):
+                normals=False, colors=False, view="normal", keep_largest=None, min_triangles=0):
     """Drop-in for run_render.render_mesh (run_render.py:970-986): per pose, the density grid and its iso-surface
     on the device, written to basedir/meshes/{i:03d}.ply in the reference's vertices / res - .5 coordinates.
     Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it).
     `normals` / `colors` / `view`: as RayCaster.extract_mesh; the attributes go into the PLYs (nx / ny / nz,
-    red / green / blue) and the list holds (vertices, triangles, attrs)."""
+    red / green / blue) and the list holds (vertices, triangles, attrs).  `keep_largest` / `min_triangles`: the
+    component filter of RayCaster.extract_mesh (keep_largest=1: the body without floaters)."""
     ray_caster = render_kwargs["ray_caster"]
     os.makedirs(os.path.join(basedir, "meshes"), exist_ok=True)
     kps, skts, bones = tensor_data["kp"], tensor_data["skts"], tensor_data["bones"]
     extras = dict(normals=normals, colors=colors, view=view) if (normals or colors) else {}
+    keeps = (dict(keep_largest=keep_largest, min_triangles=min_triangles)
+             if (keep_largest is not None or min_triangles > 0) else {})
     v_t_tuples = []
     for i in range(len(kps)):
         out = ray_caster.extract_mesh(kps[i:i + 1], skts[i:i + 1], None if bones is None else bones[i:i + 1],
-                                      radius=radius, res=res, threshold=threshold, **extras)
+                                      radius=radius, res=res, threshold=threshold, **extras, **keeps)
         attrs = out[2] if extras else {}
         write_ply(os.path.join(basedir, "meshes", f"{i:03d}.ply"), out[0], out[1], normals=attrs.get("normals"),
                   colors=attrs.get("colors"))

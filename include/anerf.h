@@ -26,6 +26,8 @@
  *   anerf_isosurface_emit   (the grid's iso-surface as an indexed mesh, ABI 20)
  *   anerf_isosurface_normals   per-vertex normals of that mesh from the grid's gradient (ABI 21; the reference's
  *                           viewer accumulates face normals on the host)       render_mesh.py:35-53
+ *   anerf_mesh_components,  the connected components of that mesh and its stable compaction (ABI 22; the reference
+ *   anerf_mesh_compact_*    leaves floaters and cavities to the user: trimesh's split() on the host)
  *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
  *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
@@ -69,7 +71,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 21
+#define ANERF_ABI_VERSION 22
 
 enum {
     ANERF_OK = 0,
@@ -382,6 +384,49 @@ int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2,
  *             squared length that underflows to 0 or overflows). */
 int anerf_isosurface_normals(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
                              const void* ws, size_t ws_bytes, float* normals, int64_t max_vertices, void* stream);
+
+/* ABI 22: the connected components of an indexed triangle mesh (triangles int32 [n_tri][3], vertex ids in
+ * [0, n_vertices)) -- what the reference leaves to trimesh's split() on the host, for dropping the detached blobs
+ * ("floaters") and cavity surfaces of a noisy density's iso-surface.  Two vertices are in one component iff a chain
+ * of triangle edges links them; a vertex no triangle uses is a component of its own with 0 triangles.
+ *   root [n_vertices]        the SMALLEST vertex id of the vertex's component (root[r] == r marks a component);
+ *   tri_count [n_vertices]   at r == root[r] the component's triangles (a triangle belongs to the component of its
+ *                            first vertex), 0 elsewhere;
+ *   vert_count [n_vertices]  at r == root[r] the component's vertices, 0 elsewhere;
+ *   n_components             device, one int64: the number of components.
+ * A lock-free union-find over the triangle list (the larger root hooked under the smaller, so the result does not
+ * depend on the schedule) and integer tallies: the outputs are the same on every run.  Precondition: ids lie in
+ * [0, n_vertices); a triangle with an id outside is skipped by every kernel (it links nothing and is counted
+ * nowhere), so a bad list cannot write out of bounds.  n_tri == 0 and n_vertices == 0 are valid (an array may be
+ * NULL where its extent is 0).  ws: anerf_mesh_components_workspace(n_vertices, n_tri) bytes, 4-byte aligned
+ * (the size query returns 0, with a message, for counts outside [0, 2^31), and 0 for n_vertices == 0).
+ * Allocation-free, asynchronous on `stream`.  ANERF_EINVAL, before any HIP call, for a count outside [0, 2^31), a
+ * NULL pointer with a non-zero extent, a NULL n_components, a short or misaligned workspace. */
+size_t anerf_mesh_components_workspace(int64_t n_vertices, int64_t n_tri);
+int anerf_mesh_components(const int32_t* triangles, int64_t n_tri, int64_t n_vertices, int32_t* root, int32_t* tri_count,
+                          int32_t* vert_count, int64_t* n_components, void* ws, size_t ws_bytes, void* stream);
+
+/* ABI 22: stable compaction of such a mesh under a vertex mask keep uint8 [n_vertices]: a vertex survives iff
+ * keep[v] != 0, a triangle iff all three of its vertices do (a triangle with an id outside [0, n_vertices) never).
+ * Both outputs keep their original relative order (count -> scan -> emit, no atomics):
+ *   vertex_map [n_vertices]       the vertex's new id, or -1;
+ *   kept [V']                     the surviving vertices' old ids, ascending (the gather index of every per-vertex
+ *                                 array: positions, normals, colours);
+ *   triangles_out [T'][3]         the surviving triangles, ids through vertex_map.
+ * anerf_mesh_compact_count writes totals_dev (device, int64 [2]: V', T') and leaves the block offsets in ws; the
+ * caller reads the 16 bytes (the one synchronisation), allocates, and calls anerf_mesh_compact_emit with the SAME
+ * keep, lists and ws.  max_kept / max_triangles are the capacities in rows (in [0, 2^31); an output may be NULL
+ * where its capacity is 0): no store goes past them, rows beyond them are dropped.  ws:
+ * anerf_mesh_compact_workspace(n_vertices, n_tri) bytes, 8-byte aligned (never 0 for valid counts: empty lists
+ * still get their totals; 0, with a message, for counts outside [0, 2^31)).  Allocation-free, asynchronous on
+ * `stream`.  ANERF_EINVAL, before any HIP call, for a count or capacity outside [0, 2^31), a NULL pointer with a
+ * non-zero extent, a NULL or misaligned or short workspace. */
+size_t anerf_mesh_compact_workspace(int64_t n_vertices, int64_t n_tri);
+int anerf_mesh_compact_count(const uint8_t* keep, int64_t n_vertices, const int32_t* triangles, int64_t n_tri, void* ws,
+                             size_t ws_bytes, int64_t* totals_dev, void* stream);
+int anerf_mesh_compact_emit(const uint8_t* keep, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                            const void* ws, size_t ws_bytes, int32_t* vertex_map, int32_t* kept, int64_t max_kept,
+                            int32_t* triangles_out, int64_t max_triangles, void* stream);
 
 /* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
  * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /

@@ -1,0 +1,138 @@
+"""Meshes and expected results shared by test_mesh_components.py (CPU) and test_gpu_mesh_components.py."""
+import functools
+import importlib
+
+import numpy as np
+
+import _iso_cases as C
+
+meshops = importlib.import_module("a-nerf_amd.meshops")
+
+# name -> ((field function, *args), threshold, expected components): isosurface_reference meshes of _iso_cases' fields
+MESHES = {
+    "sphere": (("sphere_field",), 0.0, 1),
+    "torus": (("torus_field",), 0.0, 1),
+    "two_spheres": (("two_spheres_field",), 0.0, 2),
+    "blobs": (("blobs_field",), 0.5, 5),
+    "random33": (("random_field", 5, (33, 31, 35)), 0.5, 358),
+}
+
+
+def _ro(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+def mesh(name):
+    """(vertices, triangles) of a named mesh (computed once per session, read-only)."""
+    (fn, *args), thr, _ = MESHES[name]
+    return C.reference(fn, *args, threshold=thr)
+
+
+@functools.lru_cache(maxsize=None)
+def components(name):
+    """mesh_components_reference of a named mesh, computed once per session (read-only arrays)."""
+    v, t = mesh(name)
+    comp = meshops.mesh_components_reference(t, len(v))
+    _ro(*comp)
+    return comp
+
+
+@functools.lru_cache(maxsize=None)
+def permutation(n, kind):
+    """A fixed relabelling of n vertex ids: old id -> new id."""
+    p = np.arange(n)[::-1].copy() if kind == "reversed" else np.random.default_rng(1234).permutation(n)
+    return _ro(p.astype(np.int64))[0]
+
+
+def relabel(tri, perm):
+    return np.ascontiguousarray(perm[np.asarray(tri, np.int64)].astype(np.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def relabelled(name, kind):
+    """(triangles, V, mesh_components_reference) of a named mesh with vertex v renamed permutation(V, kind)[v]."""
+    v, t = mesh(name)
+    tri = relabel(t, permutation(len(v), kind))
+    comp = meshops.mesh_components_reference(tri, len(v))
+    _ro(tri, *comp)
+    return tri, len(v), comp
+
+
+# ------------------------------------------------------------------ lists whose answer is known by construction
+STRIP_T = 300000  # (300,002 vertices: more than one 256 x 1024 tile of the block-sum scan)
+
+
+@functools.lru_cache(maxsize=None)
+def strip(shuffled=False):
+    """One strip (i, i + 1, i + 2): (triangles, V, components).  One component with root 0, ids shuffled or not."""
+    nv = STRIP_T + 2
+    tri = (np.arange(STRIP_T, dtype=np.int64)[:, None] + np.arange(3)).astype(np.int32)
+    if shuffled:
+        tri = relabel(tri, np.random.default_rng(99).permutation(nv))
+    comp = meshops.MeshComponents(np.zeros(nv, np.int32), np.zeros(1, np.int32), np.array([STRIP_T], np.int64),
+                                  np.array([nv], np.int64))
+    return _ro(tri)[0], nv, comp
+
+
+@functools.lru_cache(maxsize=None)
+def disjoint(n=5000):
+    """n triangles (4 i, 4 i + 1, 4 i + 2), vertex 4 i + 3 isolated: 2 n components over many workgroups."""
+    i = np.arange(n, dtype=np.int64)
+    tri = (4 * i[:, None] + np.arange(3)).astype(np.int32)
+    labels = np.empty(4 * n, np.int32)
+    labels.reshape(n, 4)[:, :3] = i[:, None]
+    labels.reshape(n, 4)[:, 3] = n + i
+    comp = meshops.MeshComponents(labels, np.concatenate([4 * i, 4 * i + 3]).astype(np.int32),
+                                  np.concatenate([np.ones(n), np.zeros(n)]).astype(np.int64),
+                                  np.concatenate([np.full(n, 3), np.ones(n)]).astype(np.int64))
+    return _ro(tri)[0], 4 * n, comp
+
+
+def _small(tri, nv):
+    tri = np.asarray(tri, np.int32).reshape(-1, 3)
+    return tri, nv, meshops.mesh_components_reference(tri, nv)
+
+
+def synthetic(name):
+    """(triangles, V, components) of a named synthetic list."""
+    if name == "strip":
+        return strip()
+    if name == "strip_shuffled":
+        return strip(True)
+    if name == "disjoint":
+        return disjoint()
+    return _small(*{"no_triangles": ([], 7), "no_vertices": ([], 0), "one_triangle": ([[4, 2, 3]], 6),
+                    "degenerate": ([[1, 1, 3]], 4), "duplicated": ([[0, 1, 2], [0, 1, 2]], 3)}[name])
+
+
+SYNTHETIC = ("strip", "strip_shuffled", "disjoint", "no_triangles", "no_vertices", "one_triangle", "degenerate",
+             "duplicated")
+
+
+# ------------------------------------------------------------------ the filter, written out independently
+def attributes(nv, seed=5):
+    """A float32 [V, 3] and a uint8 [V, 3] per-vertex attribute."""
+    rng = np.random.default_rng(seed)
+    return rng.random((nv, 3)).astype(np.float32), rng.integers(0, 256, (nv, 3)).astype(np.uint8)
+
+
+def compact_expected(keep, tri):
+    """(vertex_map, kept, triangles) of the compaction contract."""
+    keep = np.asarray(keep) != 0
+    tri = np.asarray(tri, np.int64).reshape(-1, 3)
+    kept = np.nonzero(keep)[0].astype(np.int32)
+    vertex_map = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+    alive = keep[tri].all(axis=1) if len(tri) else np.zeros(0, bool)
+    return vertex_map, kept, vertex_map[tri[alive]].astype(np.int32).reshape(-1, 3)
+
+
+def filter_expected(comp, tri, keep_largest, min_triangles):
+    """(keep mask [V], kept, triangles) of the filter's rule on known components."""
+    ok = comp.triangle_counts >= min_triangles
+    if keep_largest is not None:
+        ok = ok & (np.arange(len(ok)) < keep_largest)
+    keep = ok[comp.labels.astype(np.int64)] if len(comp.labels) else np.zeros(0, bool)
+    _, kept, out = compact_expected(keep, tri)
+    return keep, kept, out

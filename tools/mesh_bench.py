@@ -11,12 +11,20 @@ pass, no host read), and colors_ms, RayCaster.render_pts_radiance at the mesh's 
 against its own normal (colors_points of them) -- what extract_mesh(normals=True, colors=True) adds to the grid
 and the extraction.  Both are short, so they are timed over 20 repetitions.
 
+The component filter (meshops.py) is four more: components_kernels_ms, the launches of anerf_mesh_components alone (no
+host read); components_ms, meshops.mesh_components whole (the id range check, the kernels, the host read of the
+count, ranking with torch); compact_ms, meshops.compact_mesh under keep_largest=1's mask (count, one host read,
+emit); filter_mesh_ms, filter_mesh(keep_largest=1) on positions and normals -- what extract_mesh(keep_largest=1) adds
+(extract_mesh_keep_largest_ms is that call).  components_reference_host_ms is mesh_components_reference (NumPy) on
+the same mesh, once, for scale.
+
 Prints one JSON line, and appends it to the file given with --append (the record: profiles/mesh_bench.jsonl).
 Usage: python tools/mesh_bench.py [res] [precision] [--append FILE]"""
 import importlib
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -26,6 +34,7 @@ sys.path.insert(0, REPO)
 anerf = importlib.import_module("a-nerf_amd")
 syn = importlib.import_module("a-nerf_amd.synthetic")
 iso = importlib.import_module("a-nerf_amd.isosurface")
+meshops = importlib.import_module("a-nerf_amd.meshops")
 
 
 def _time(fn, reps=5):
@@ -61,6 +70,41 @@ def _normals_leg(grid, thr):
     return ms
 
 
+def _components_leg(t, nv):
+    """The launches of anerf_mesh_components alone, into preallocated outputs."""
+    _lib = importlib.import_module("a-nerf_amd._lib")
+    lib = _lib.load()
+    nt = int(t.shape[0])
+    root, tc, vc = (torch.empty(nv, device=t.device, dtype=torch.int32) for _ in range(3))
+    n_comp = torch.empty(1, device=t.device, dtype=torch.int64)
+    need = lib.anerf_mesh_components_workspace(nv, nt)
+    ws = torch.empty(need, device=t.device, dtype=torch.uint8)
+    ms, _ = _time(lambda: _lib.check(lib.anerf_mesh_components(
+        _lib.ptr(t), nt, nv, _lib.ptr(root), _lib.ptr(tc), _lib.ptr(vc), _lib.ptr(n_comp), _lib.ptr(ws), need,
+        _lib.stream_handle(t.device)), "anerf_mesh_components"), reps=20)
+    return ms
+
+
+def _filter_legs(rc, kps, skts, res, thr, v, t, nrm):
+    nv = int(v.shape[0])
+    kernels_ms = _components_leg(t, nv)
+    comp_ms, comp = _time(lambda: meshops.mesh_components(t, nv), reps=20)
+    keep = (comp.labels == 0).to(torch.uint8)
+    compact_ms, (_, kept, kt) = _time(lambda: meshops.compact_mesh(keep, t), reps=20)
+    filter_ms, _ = _time(lambda: meshops.filter_mesh(v, t, [nrm], keep_largest=1), reps=20)
+    keep_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, keep_largest=1))
+    t_host = t.cpu().numpy()
+    t0 = time.perf_counter()
+    ref = meshops.mesh_components_reference(t_host, nv)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    assert np.array_equal(ref.labels, comp.labels.cpu().numpy())
+    return {"components": int(comp.roots.shape[0]), "largest_component_triangles": int(comp.triangle_counts[0]),
+            "kept_vertices": int(kept.shape[0]), "kept_triangles": int(kt.shape[0]),
+            "components_kernels_ms": round(kernels_ms, 3), "components_ms": round(comp_ms, 3),
+            "compact_ms": round(compact_ms, 3), "filter_mesh_ms": round(filter_ms, 3),
+            "extract_mesh_keep_largest_ms": round(keep_ms, 3), "components_reference_host_ms": round(ref_ms, 1)}
+
+
 def main():
     argv = list(sys.argv[1:])
     append = None
@@ -85,6 +129,8 @@ def main():
     colors_ms, raw = _time(lambda: rc.render_pts_radiance(vw, dirs, kps, skts, None), reps=20)
     attrs_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, normals=True,
                                                 colors=True))
+    _, ti, ni = iso.isosurface(grid, thr, relu=True, normals=True)
+    legs = _filter_legs(rc, kps, skts, res, thr, v, ti, ni)
     n = (res + 1) ** 3
     line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
                       "grid_ms": round(grid_ms, 3), "isosurface_ms": round(iso_ms, 3),
@@ -95,7 +141,8 @@ def main():
                       "normals_ms": round(normals_ms, 3), "colors_ms": round(colors_ms, 3),
                       "colors_points": int(raw.shape[0]), "normals_over_grid": round(normals_ms / grid_ms, 4),
                       "colors_over_grid": round(colors_ms / grid_ms, 4),
-                      "extract_mesh_normals_colors_ms": round(attrs_ms, 3)})
+                      "extract_mesh_normals_colors_ms": round(attrs_ms, 3), **legs,
+                      "filter_over_grid": round(legs["filter_mesh_ms"] / grid_ms, 4)})
     print(line, flush=True)
     if append:
         with open(append, "a") as f:
