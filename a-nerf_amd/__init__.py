@@ -9,11 +9,13 @@ from .config import RenderConfig, flops_per_sample, samples_per_ray
 from .raycaster import RayCaster, create_raycaster, load_checkpoint
 from .render import batchify_rays, render, render_path, render_frames
 from .isosurface import isosurface, isosurface_reference, mesh_from_grid, read_ply, render_mesh, write_ply
-from .meshops import filter_mesh, mesh_components, mesh_components_reference
+from .meshops import (filter_mesh, mesh_components, mesh_components_reference, smooth_mesh, smooth_mesh_reference,
+                      vertex_adjacency, vertex_adjacency_reference)
 from . import dataset, rays, synthetic, train
 from .dataset import RayImageDataset, RayImageSampler
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
            "isosurface", "isosurface_reference", "mesh_from_grid", "read_ply", "render_mesh", "write_ply",
-           "mesh_components", "mesh_components_reference", "filter_mesh"]
+           "mesh_components", "mesh_components_reference", "filter_mesh", "vertex_adjacency",
+           "vertex_adjacency_reference", "smooth_mesh", "smooth_mesh_reference"]

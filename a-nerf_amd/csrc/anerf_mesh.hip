@@ -1,4 +1,5 @@
-// anerf_mesh.hip — connected components of an indexed triangle mesh and its stable compaction, on the device.
+// anerf_mesh.hip — connected components of an indexed triangle mesh and its stable compaction, its vertex adjacency
+// (CSR) and Laplacian / Taubin smoothing over it, on the device.
 //
 // The iso-surface of a noisy density (anerf_iso.hip) is the body plus detached blobs and closed cavity surfaces;
 // the reference leaves them to trimesh's split() on the host.  Here the triangle list stays in HBM:
@@ -16,6 +17,17 @@
 //                             scan_kernel      exclusive scan of the block sums (one workgroup, 64-bit), the totals
 //   anerf_mesh_compact_emit   vertex_kernel    the same flags scanned within the block: vertex_map, kept
 //                             triangle_kernel  the surviving triangles, ids through vertex_map (separate launch)
+//
+//   anerf_mesh_adjacency_count  adj_count_kernel   per triangle: the pairs it lists, counted per vertex (int atomics)
+//                             (scan)             the raw row offsets: tile sums, one workgroup, per-tile scan
+//                             adj_fill_kernel    the raw rows through per-vertex cursors, in arrival order
+//                             adj_rows_kernel    per vertex: a row of <= 64 raw entries sorted by its thread, the
+//                                                distinct count and the boundary flag from its runs; longer rows listed
+//                             adj_long_rows_kernel   per listed row: one workgroup, a bitonic network (LDS or global)
+//                             (scan)             the distinct counts -> offsets, the totals
+//   anerf_mesh_adjacency_emit   adj_emit_kernel, adj_emit_long_kernel   the distinct entries of the sorted rows
+//   anerf_mesh_smooth         smooth_step_kernel per vertex: one Jacobi step over its CSR row; one launch per step
+// (the adjacency's contract and the reason for the launch per step: further down and DESIGN.md)
 //
 // The union-find's invariants, from the end of seed_kernel on (DESIGN.md has the termination argument; the seed only
 // has to leave a forest with parent[x] <= x whose trees lie inside components -- it may drop an edge it saw, since
@@ -388,6 +400,379 @@ int launched(const char* who) {
 
 int blocks_for(long long n, int threads = NTHR) { return (int)((n + threads - 1) / threads); }
 
+// ------------------------------------------------------------------ vertex adjacency (CSR)
+constexpr int SHORT_ROW = 64;         // the raw entries one thread sorts at most; longer rows go to a workgroup
+constexpr int LDS_ROW = 8192;         // the padded length up to which a long row's network runs over LDS (32 KB)
+constexpr int MAX_LONG_BLOCKS = 1024;  // workgroups of the long-row kernels (each strides over the list)
+
+// Workspace, in ints; everything whose size depends on V alone comes first, so that anerf_mesh_adjacency_emit
+// finds it without the triangle count:
+//   raw_off[V + 1] | cnt[V] | long_list[V] | n_long | block_sum[nb] | block_max[nb] | base[nb] | raw[6 T]
+// cnt holds the listed pairs per vertex (count), counts down to 0 as the cursor of the fill, then holds the
+// distinct degree (the row kernels), which the second scan turns into `offsets`.
+struct AdjPlan {
+    int nblocks;
+    size_t raw_off, cnt, long_list, n_long, block_sum, block_max, base, raw;  // offsets in ints
+};
+
+bool adj_plan(int64_t nv, AdjPlan* pl) {
+    if (nv < 0 || nv > MAXN) return false;
+    pl->nblocks = (int)((nv + TILE - 1) / TILE);
+    if (pl->nblocks < 1) pl->nblocks = 1;  // (no vertices: offsets[0] and the totals are still written)
+    size_t o = 0;
+    pl->raw_off = o, o += (size_t)nv + 1;
+    pl->cnt = o, o += (size_t)nv;
+    pl->long_list = o, o += (size_t)nv;
+    pl->n_long = o, o += 1;
+    pl->block_sum = o, o += (size_t)pl->nblocks;
+    pl->block_max = o, o += (size_t)pl->nblocks;
+    pl->base = o, o += (size_t)pl->nblocks;
+    pl->raw = o;
+    return true;
+}
+
+__global__ __launch_bounds__(NTHR) void adj_zero_kernel(int* __restrict__ cnt, int nv, int* __restrict__ n_long) {
+    const long long v = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (v < nv) cnt[v] = 0;
+    if (v == 0) *n_long = 0;
+}
+
+// The pairs a triangle lists, per first end: (a,b) (a,c) | (b,a) (b,c) | (c,a) (c,b), equal ends dropped.
+__global__ __launch_bounds__(NTHR) void adj_count_kernel(const int* __restrict__ tri, long long nt, int nv, int* cnt) {
+    const long long i = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (i >= nt) return;
+    const int a = tri[3 * i], b = tri[3 * i + 1], c = tri[3 * i + 2];
+    if (!in_range(a, b, c, nv)) return;
+    const int na = (a != b) + (a != c), nb = (b != a) + (b != c), nc = (c != a) + (c != b);
+    if (na) atomicAdd(cnt + a, na);
+    if (nb) atomicAdd(cnt + b, nb);
+    if (nc) atomicAdd(cnt + c, nc);
+}
+
+// cnt[x] counts down: every listed pair takes a slot of its own in row x, in arrival order (sorted afterwards).
+__device__ __forceinline__ void adj_put(int* cnt, const int* __restrict__ raw_off, int* __restrict__ raw, int x,
+                                        int y) {
+    if (x == y) return;
+    const int slot = atomicSub(cnt + x, 1) - 1;
+    if (slot >= 0) raw[raw_off[x] + slot] = y;  // (slot < the row's count: inside the row)
+}
+
+__global__ __launch_bounds__(NTHR) void adj_fill_kernel(const int* __restrict__ tri, long long nt, int nv, int* cnt,
+                                                        const int* __restrict__ raw_off, int* __restrict__ raw) {
+    const long long i = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (i >= nt) return;
+    const int a = tri[3 * i], b = tri[3 * i + 1], c = tri[3 * i + 2];
+    if (!in_range(a, b, c, nv)) return;
+    adj_put(cnt, raw_off, raw, a, b);
+    adj_put(cnt, raw_off, raw, a, c);
+    adj_put(cnt, raw_off, raw, b, a);
+    adj_put(cnt, raw_off, raw, b, c);
+    adj_put(cnt, raw_off, raw, c, a);
+    adj_put(cnt, raw_off, raw, c, b);
+}
+
+// One thread per vertex: a row of at most SHORT_ROW raw entries is sorted in place (insertion sort) and walked once
+// for its distinct entries and for a run of length 1 (a pair listed once: a boundary edge); a longer row is put on
+// the list of adj_long_rows_kernel (in arrival order: each row is handled on its own, so the order does not show).
+__global__ __launch_bounds__(NTHR) void adj_rows_kernel(const int* __restrict__ raw_off, int* __restrict__ raw, int nv,
+                                                        int* __restrict__ deg, unsigned char* __restrict__ boundary,
+                                                        int* __restrict__ long_list, int* n_long) {
+    const long long v = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (v >= nv) return;
+    const int b = raw_off[v], n = raw_off[v + 1] - b;
+    if (n > SHORT_ROW) {
+        long_list[atomicAdd(n_long, 1)] = (int)v;  // (each vertex at most once: the index stays below nv)
+        return;
+    }
+    int* r = raw + b;
+    for (int i = 1; i < n; ++i) {
+        const int x = r[i];
+        int j = i;
+        for (; j > 0 && r[j - 1] > x; --j) r[j] = r[j - 1];
+        r[j] = x;
+    }
+    int d = 0, bnd = 0;
+    for (int i = 0; i < n;) {
+        int j = i + 1;
+        while (j < n && r[j] == r[i]) ++j;
+        ++d;
+        if (j - i == 1) bnd = 1;
+        i = j;
+    }
+    deg[v] = d;
+    boundary[v] = (unsigned char)bnd;
+}
+
+// Bitonic sorting network over a[0, n) by one workgroup, ascending, the row padded virtually to P = 2^lp >= n with
+// +infinity: every compare-exchange (l, r), l < r, of this form of the network leaves the smaller at l, so an
+// infinity at r >= n never moves and those pairs are skipped.  Stage s merges blocks of 2^s: pairs (i, block end - i)
+// first, then halving strides.  Only __syncthreads between the stages (over global memory as well: one workgroup,
+// one CU).  lp <= 31; every loop is bounded by P.
+__device__ __forceinline__ void compare_exchange(int* a, unsigned l, unsigned r, unsigned n) {
+    if (r >= n) return;
+    const int x = a[l], y = a[r];
+    if (x > y) {
+        a[l] = y;
+        a[r] = x;
+    }
+}
+
+__device__ __forceinline__ void bitonic_sort(int* a, unsigned n, int lp) {
+    const unsigned half = lp > 0 ? 1u << (lp - 1) : 0u;  // pairs per stage
+    for (int s = 1; s <= lp; ++s) {
+        const unsigned k = 1u << s, h = k >> 1;
+        for (unsigned t = threadIdx.x; t < half; t += NTHR) {
+            const unsigned first = (t >> (s - 1)) << s, in = t & (h - 1);
+            compare_exchange(a, first + in, first + (k - 1 - in), n);
+        }
+        __syncthreads();
+        for (int q = s - 2; q >= 0; --q) {
+            const unsigned j = 1u << q;
+            for (unsigned t = threadIdx.x; t < half; t += NTHR) {
+                const unsigned l = ((t >> q) << (q + 1)) + (t & (j - 1));
+                compare_exchange(a, l, l + j, n);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// One workgroup per listed row (strided over the list, whose length is read from the device: no host read): sorted
+// by the network, over LDS where the padded row fits and in place over global memory where not; then the distinct
+// count and the boundary flag from the sorted row, every thread looking at its entries' two neighbours.
+__global__ __launch_bounds__(NTHR) void adj_long_rows_kernel(const int* __restrict__ raw_off, int* raw, int nv,
+                                                             int* __restrict__ deg, unsigned char* __restrict__ boundary,
+                                                             const int* __restrict__ long_list,
+                                                             const int* __restrict__ n_long) {
+    __shared__ int row[LDS_ROW];
+    __shared__ int tally[2];
+    const int nl = min(*n_long, nv);
+    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // (uniform over the workgroup)
+        const int v = long_list[li];
+        if ((unsigned)v >= (unsigned)nv) continue;
+        const int b = raw_off[v];
+        const unsigned n = (unsigned)max(raw_off[v + 1] - b, 0);
+        int* g = raw + b;
+        int lp = 0;
+        while (lp < 31 && (1u << lp) < n) ++lp;
+        const bool in_lds = (1u << lp) <= (unsigned)LDS_ROW;
+        if (threadIdx.x == 0) tally[0] = tally[1] = 0;
+        if (in_lds) {
+            for (unsigned i = threadIdx.x; i < n; i += NTHR) row[i] = g[i];
+            __syncthreads();
+            bitonic_sort(row, n, lp);
+            for (unsigned i = threadIdx.x; i < n; i += NTHR) g[i] = row[i];
+        } else {
+            __syncthreads();
+            bitonic_sort(g, n, lp);
+        }
+        __syncthreads();  // (the row in global memory is complete for the whole workgroup)
+        int d = 0, single = 0;
+        for (unsigned i = threadIdx.x; i < n; i += NTHR) {
+            const int x = g[i];
+            const bool first = i == 0 || g[i - 1] != x, last = i + 1 == n || g[i + 1] != x;
+            d += first ? 1 : 0;
+            single |= (first && last) ? 1 : 0;
+        }
+        atomicAdd(&tally[0], d);
+        atomicOr(&tally[1], single);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            deg[v] = tally[0];
+            boundary[v] = (unsigned char)tally[1];
+        }
+        __syncthreads();  // (row and tally are free for the next row)
+    }
+}
+
+// Exclusive scan of in[0, n) into out[0, n] (out[n]: the sum, which fits an int: at most 6 T < 2^31), the block-sum
+// pattern of the compaction above: per-tile sums (and maxima) -> one workgroup scans them -> per-tile scan.
+__global__ __launch_bounds__(NTHR) void tile_reduce_kernel(const int* __restrict__ in, int n, int* __restrict__ block_sum,
+                                                           int* __restrict__ block_max) {
+    __shared__ int lds[NTHR];
+    __shared__ int mx;
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    int s = 0, m = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        if (first + it < n) {
+            const int x = in[first + it];
+            s += x;
+            m = max(m, x);
+        }
+    }
+    if (threadIdx.x == 0) mx = 0;
+    int total;
+    block_exclusive_scan(s, lds, total);  // (its barriers publish mx = 0)
+    atomicMax(&mx, m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_sum[blockIdx.x] = total;
+        block_max[blockIdx.x] = mx;
+    }
+}
+
+__global__ __launch_bounds__(NTHR) void base_scan_kernel(const int* __restrict__ block_sum,
+                                                         const int* __restrict__ block_max, int nblocks,
+                                                         int* __restrict__ base, int* __restrict__ last,
+                                                         long long* __restrict__ totals) {
+    __shared__ int lds[NTHR];
+    __shared__ int mx;
+    if (threadIdx.x == 0) mx = 0;
+    __syncthreads();
+    int carry = 0, m = 0;
+    for (int start = 0; start < nblocks; start += NTHR) {
+        const int b = start + threadIdx.x;
+        const int c = b < nblocks ? block_sum[b] : 0;
+        if (b < nblocks) m = max(m, block_max[b]);
+        int total;
+        const int e = block_exclusive_scan(c, lds, total);
+        if (b < nblocks) base[b] = carry + e;
+        carry += total;
+    }
+    atomicMax(&mx, m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *last = carry;
+        if (totals) {
+            totals[0] = carry;
+            totals[1] = mx;
+        }
+    }
+}
+
+__global__ __launch_bounds__(NTHR) void tile_scan_kernel(const int* __restrict__ in, int n, const int* __restrict__ base,
+                                                         int* __restrict__ out) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    int x[ITEMS], s = 0;
+    for (int it = 0; it < ITEMS; ++it) {
+        x[it] = first + it < n ? in[first + it] : 0;
+        s += x[it];
+    }
+    int total;
+    int e = base[blockIdx.x] + block_exclusive_scan(s, lds, total);
+    for (int it = 0; it < ITEMS; ++it) {
+        if (first + it >= n) break;
+        out[first + it] = e;
+        e += x[it];
+    }
+}
+
+void adj_scan(const AdjPlan& pl, int* w, const int* in, int n, int* out, long long* totals, hipStream_t s) {
+    hipLaunchKernelGGL(tile_reduce_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, in, n, w + pl.block_sum,
+                       w + pl.block_max);
+    hipLaunchKernelGGL(base_scan_kernel, dim3(1), dim3(NTHR), 0, s, (const int*)(w + pl.block_sum),
+                       (const int*)(w + pl.block_max), pl.nblocks, w + pl.base, out + n, totals);
+    if (n > 0)
+        hipLaunchKernelGGL(tile_scan_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, in, n, (const int*)(w + pl.base), out);
+}
+
+// A row of the emit pass: its bounds clamped to the part of the workspace that holds the raw rows (the emit entry
+// does not know T; a workspace that is not the count pass's cannot make it read outside).
+__device__ __forceinline__ int clamp_raw(int x, long long raw_cap) {
+    return x < 0 ? 0 : (x > raw_cap ? (int)raw_cap : x);
+}
+
+// One thread per vertex: the distinct entries of a sorted short row, to neighbors[offsets[v] ...].
+__global__ __launch_bounds__(NTHR) void adj_emit_kernel(const int* __restrict__ raw_off, const int* __restrict__ raw,
+                                                        int nv, long long raw_cap, const int* __restrict__ offsets,
+                                                        int* __restrict__ neighbors, long long max_neighbors) {
+    const long long v = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (v >= nv) return;
+    const int b = clamp_raw(raw_off[v], raw_cap), n = clamp_raw(raw_off[v + 1], raw_cap) - b;
+    if (n > SHORT_ROW) return;  // (adj_emit_long_kernel's)
+    const int* r = raw + b;
+    long long pos = offsets[v];
+    const long long end = min((long long)offsets[v + 1], max_neighbors);
+    int prev = 0;
+    for (int i = 0; i < n; ++i) {
+        const int x = r[i];
+        if (i == 0 || x != prev) {
+            if (pos >= 0 && pos < end) neighbors[pos] = x;
+            ++pos;
+        }
+        prev = x;
+    }
+}
+
+// One workgroup per listed long row: tiles of NTHR entries, the "first of its run" flags scanned within the tile.
+__global__ __launch_bounds__(NTHR) void adj_emit_long_kernel(const int* __restrict__ raw_off,
+                                                             const int* __restrict__ raw, int nv, long long raw_cap,
+                                                             const int* __restrict__ long_list,
+                                                             const int* __restrict__ n_long,
+                                                             const int* __restrict__ offsets, int* __restrict__ neighbors,
+                                                             long long max_neighbors) {
+    __shared__ int lds[NTHR];
+    const int nl = min(*n_long, nv);
+    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // (uniform over the workgroup)
+        const int v = long_list[li];
+        if ((unsigned)v >= (unsigned)nv) continue;
+        const int b = clamp_raw(raw_off[v], raw_cap), n = clamp_raw(raw_off[v + 1], raw_cap) - b;
+        const int* r = raw + b;
+        const long long end = min((long long)offsets[v + 1], max_neighbors);
+        long long carry = offsets[v];
+        for (long long start = 0; start < n; start += NTHR) {
+            const long long i = start + threadIdx.x;
+            const bool first = i < n && (i == 0 || r[i] != r[i - 1]);
+            int total;
+            const long long pos = carry + block_exclusive_scan(first ? 1 : 0, lds, total);
+            if (first && pos >= 0 && pos < end) neighbors[pos] = r[i];
+            carry += total;
+        }
+    }
+}
+
+int long_blocks(long long raw_entries) {
+    const long long rows = raw_entries / (SHORT_ROW + 1);  // no more rows than this can be long
+    return (int)(rows < 1 ? 1 : (rows > MAX_LONG_BLOCKS ? MAX_LONG_BLOCKS : rows));
+}
+
+// ------------------------------------------------------------------ smoothing
+// One Jacobi step p' = p + w (mean of the neighbours - p), one thread per vertex; the sum runs over the row in its
+// stored (ascending) order, every operation separately rounded (-ffp-contract=off), the division correctly rounded.
+// A bad CSR cannot make it read outside: row bounds are clamped to [0, ne], a neighbour outside [0, nv) is skipped
+// and not counted.
+__global__ __launch_bounds__(NTHR) void smooth_step_kernel(const float* __restrict__ p, int nv,
+                                                           const int* __restrict__ offsets,
+                                                           const int* __restrict__ neighbors, int ne,
+                                                           const unsigned char* __restrict__ pinned, float w,
+                                                           float* __restrict__ out) {
+    const long long v = (long long)blockIdx.x * NTHR + threadIdx.x;
+    if (v >= nv) return;
+    const float x = p[3 * v], y = p[3 * v + 1], z = p[3 * v + 2];
+    float ox = x, oy = y, oz = z;
+    if (!(pinned && pinned[v])) {
+        const int b = min(max(offsets[v], 0), ne), e = min(max(offsets[v + 1], 0), ne);
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        int d = 0;
+        for (int k = b; k < e; ++k) {
+            const int u = neighbors[k];
+            if ((unsigned)u >= (unsigned)nv) continue;
+            const float ux = p[3 * (long long)u], uy = p[3 * (long long)u + 1], uz = p[3 * (long long)u + 2];
+            if (d == 0) {
+                sx = ux, sy = uy, sz = uz;
+            } else {
+                sx = sx + ux, sy = sy + uy, sz = sz + uz;
+            }
+            ++d;
+        }
+        if (d > 0) {
+            const float fd = (float)d;
+            ox = x + w * (__fdiv_rn(sx, fd) - x);
+            oy = y + w * (__fdiv_rn(sy, fd) - y);
+            oz = z + w * (__fdiv_rn(sz, fd) - z);
+        }
+    }
+    out[3 * v] = ox;
+    out[3 * v + 1] = oy;
+    out[3 * v + 2] = oz;
+}
+
+bool overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + bytes && y < x + bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -488,6 +873,137 @@ int anerf_mesh_compact_emit(const uint8_t* keep, int64_t n_vertices, const int32
         hipLaunchKernelGGL(triangle_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, l, base + pl.nblocks,
                            (const int*)vertex_map, triangles_out, (long long)max_triangles);
     return launched("anerf_mesh_compact_emit");
+}
+
+size_t anerf_mesh_adjacency_workspace(int64_t n_vertices, int64_t n_tri) {
+    AdjPlan pl;
+    if (!adj_plan(n_vertices, &pl) || n_tri < 0 || n_tri > MAXN / 6) {
+        anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_workspace: n_vertices must be in [0, 2^31) and "
+                                          "6 n_tri below 2^31");
+        return 0;
+    }
+    return (pl.raw + (size_t)6 * (size_t)n_tri) * sizeof(int);
+}
+
+int anerf_mesh_adjacency_count(const int32_t* triangles, int64_t n_tri, int64_t n_vertices, void* ws, size_t ws_bytes,
+                               int32_t* offsets, uint8_t* boundary, int64_t* totals_dev, void* stream) {
+    char msg[256];
+    AdjPlan pl;
+    if (!adj_plan(n_vertices, &pl) || n_tri < 0 || n_tri > MAXN / 6) {
+        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_count: n_vertices %lld must be in [0, 2^31) and 6 n_tri "
+                 "(n_tri %lld) below 2^31", (long long)n_vertices, (long long)n_tri);
+        return anerf_internal_fail(ANERF_EINVAL, msg);
+    }
+    if (!offsets || !totals_dev || !ws || (n_tri > 0 && !triangles) || (n_vertices > 0 && !boundary))
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: NULL offsets, totals or workspace, or "
+                                                 "NULL triangles or boundary with a non-zero extent");
+    if ((uintptr_t)ws % 4)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: the workspace must be 4-byte aligned");
+    const size_t need = (pl.raw + (size_t)6 * (size_t)n_tri) * sizeof(int);
+    if (ws_bytes < need) {
+        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_count: workspace of %zu bytes, %zu needed "
+                 "(anerf_mesh_adjacency_workspace)", ws_bytes, need);
+        return anerf_internal_fail(ANERF_EINVAL, msg);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nv = (int)n_vertices;
+    const long long nt = (long long)n_tri;
+    int* w = (int*)ws;
+    int *raw_off = w + pl.raw_off, *cnt = w + pl.cnt, *long_list = w + pl.long_list, *n_long = w + pl.n_long;
+    int* raw = w + pl.raw;
+    const bool pairs = nv > 0 && nt > 0;
+    hipLaunchKernelGGL(adj_zero_kernel, dim3(nv > 0 ? blocks_for(nv) : 1), dim3(NTHR), 0, s, cnt, nv, n_long);
+    if (pairs) hipLaunchKernelGGL(adj_count_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, cnt);
+    adj_scan(pl, w, cnt, nv, raw_off, nullptr, s);
+    if (pairs)
+        hipLaunchKernelGGL(adj_fill_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, cnt,
+                           (const int*)raw_off, raw);
+    if (nv > 0) {
+        hipLaunchKernelGGL(adj_rows_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, (const int*)raw_off, raw, nv, cnt,
+                           boundary, long_list, n_long);
+        if (6 * nt > SHORT_ROW)
+            hipLaunchKernelGGL(adj_long_rows_kernel, dim3(long_blocks(6 * nt)), dim3(NTHR), 0, s, (const int*)raw_off,
+                               raw, nv, cnt, boundary, (const int*)long_list, (const int*)n_long);
+    }
+    adj_scan(pl, w, cnt, nv, offsets, (long long*)totals_dev, s);
+    return launched("anerf_mesh_adjacency_count");
+}
+
+int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, const int32_t* offsets,
+                              int32_t* neighbors, int64_t max_neighbors, void* stream) {
+    char msg[256];
+    AdjPlan pl;
+    if (!adj_plan(n_vertices, &pl) || max_neighbors < 0 || max_neighbors > MAXN) {
+        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_emit: n_vertices %lld / max_neighbors %lld must be in "
+                 "[0, 2^31)", (long long)n_vertices, (long long)max_neighbors);
+        return anerf_internal_fail(ANERF_EINVAL, msg);
+    }
+    if (!offsets || !ws || (max_neighbors > 0 && !neighbors))
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: NULL offsets or workspace, or NULL "
+                                                 "neighbors with a non-zero capacity");
+    if ((uintptr_t)ws % 4)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: the workspace must be 4-byte aligned");
+    if (ws_bytes < pl.raw * sizeof(int)) {
+        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_emit: workspace of %zu bytes, at least %zu needed "
+                 "(anerf_mesh_adjacency_workspace)", ws_bytes, pl.raw * sizeof(int));
+        return anerf_internal_fail(ANERF_EINVAL, msg);
+    }
+    const int nv = (int)n_vertices;
+    if (nv == 0 || max_neighbors == 0) return ANERF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int* w = (const int*)ws;
+    long long raw_cap = (long long)(ws_bytes / sizeof(int) - pl.raw);  // the raw rows the workspace can hold
+    if (raw_cap > MAXN) raw_cap = MAXN;
+    hipLaunchKernelGGL(adj_emit_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, w + pl.raw_off, w + pl.raw, nv, raw_cap,
+                       offsets, neighbors, (long long)max_neighbors);
+    if (raw_cap > SHORT_ROW)
+        hipLaunchKernelGGL(adj_emit_long_kernel, dim3(long_blocks(raw_cap)), dim3(NTHR), 0, s, w + pl.raw_off,
+                           w + pl.raw, nv, raw_cap, w + pl.long_list, w + pl.n_long, offsets, neighbors,
+                           (long long)max_neighbors);
+    return launched("anerf_mesh_adjacency_emit");
+}
+
+int anerf_mesh_smooth(const float* positions, int64_t n_vertices, const int32_t* offsets, const int32_t* neighbors,
+                      int64_t n_neighbors, const uint8_t* pinned, int32_t iterations, float lambda, float mu,
+                      int32_t flags, float* out, float* scratch, void* stream) {
+    char msg[256];
+    if (n_vertices < 0 || n_vertices > MAXN || n_neighbors < 0 || n_neighbors > MAXN || iterations < 0 ||
+        iterations > 0x3fffffff || (flags & ~ANERF_SMOOTH_TAUBIN)) {
+        snprintf(msg, sizeof msg, "anerf_mesh_smooth: n_vertices %lld / n_neighbors %lld must be in [0, 2^31), "
+                 "iterations %d in [0, 2^30), flags %d a combination of ANERF_SMOOTH_*", (long long)n_vertices,
+                 (long long)n_neighbors, (int)iterations, (int)flags);
+        return anerf_internal_fail(ANERF_EINVAL, msg);
+    }
+    const int steps = iterations * ((flags & ANERF_SMOOTH_TAUBIN) ? 2 : 1);
+    if (n_vertices > 0 && (!positions || !out || !offsets || (steps > 1 && !scratch)))
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_smooth: NULL positions, out or offsets, or NULL scratch "
+                                                 "with more than one step");
+    if (n_neighbors > 0 && !neighbors)
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_smooth: NULL neighbors with a non-zero extent");
+    const size_t bytes = (size_t)n_vertices * 3 * sizeof(float);
+    if (overlap(positions, out, bytes) || overlap(positions, scratch, bytes) || overlap(out, scratch, bytes))
+        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_smooth: positions, out and scratch must not overlap");
+    if (n_vertices == 0) return ANERF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int nv = (int)n_vertices;
+    if (steps == 0) {
+        const hipError_t e = hipMemcpyAsync(out, positions, bytes, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) {
+            snprintf(msg, sizeof msg, "anerf_mesh_smooth: %s", hipGetErrorString(e));
+            return anerf_internal_fail(ANERF_EHIP, msg);
+        }
+        return ANERF_OK;
+    }
+    // step i writes `out` when an even number of steps follows it: the last one always does
+    const float* src = positions;
+    for (int i = 0; i < steps; ++i) {
+        float* dst = ((steps - 1 - i) & 1) ? scratch : out;
+        const float w = ((flags & ANERF_SMOOTH_TAUBIN) && (i & 1)) ? mu : lambda;
+        hipLaunchKernelGGL(smooth_step_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, src, nv, offsets, neighbors,
+                           (int)n_neighbors, pinned, w, dst);
+        src = dst;
+    }
+    return launched("anerf_mesh_smooth");
 }
 
 }  // extern "C"

@@ -290,7 +290,8 @@ def read_ply(path, attributes=False):
 
 
 def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False, normals=False, colors=False,
-                   view="normal", cams=None, radiance=None, keep_largest=None, min_triangles=0):
+                   view="normal", cams=None, radiance=None, keep_largest=None, min_triangles=0, smooth=0,
+                   smooth_lambda=0.5, smooth_mu=-0.53):
     """extract_mesh's second half: the iso-surface of a caster's render_mesh_density grid (relu on load, as
     run_render.render_mesh's np.maximum(raw_d, 0)) in the requested coordinates:
       "index"  array-index coordinates, as mcubes.marching_cubes;
@@ -309,7 +310,12 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     `keep_largest` / `min_triangles` drop connected components (meshops.filter_mesh: keep_largest=1 keeps the body
     and drops the floaters and cavity surfaces of a noisy density) right after the extraction, before the colour
     query: dropped vertices cost no radiance work, and the normals returned are the kept rows.  With the defaults
-    that code is not entered."""
+    that code is not entered.
+    `smooth` > 0 runs that many Taubin iterations (meshops.smooth_mesh with lam=smooth_lambda, mu=smooth_mu,
+    pin="boundary"; smooth_mu=None: plain Laplacian) right after the component filter, in index coordinates, before
+    the `unit` / `world` mapping: the colours are queried at the smoothed world vertices.  attrs["normals"] stay the
+    gradient normals of the UNSMOOTHED crossing (face-based normals of the smoothed surface are not computed), and
+    they still give the view directions of view="normal".  With smooth=0 that code is not entered."""
     if coords not in ("unit", "index", "world"):
         raise ValueError(f"coords must be 'unit', 'index' or 'world', got {coords!r}")
     one_dir = None
@@ -333,6 +339,9 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
             v, t = filter_mesh(v, t, keep_largest=keep_largest, min_triangles=min_triangles)
         else:
             v, t, (n,) = filter_mesh(v, t, [n], keep_largest=keep_largest, min_triangles=min_triangles)
+    if smooth != 0:  # (a negative count is smooth_mesh's ValueError)
+        from .meshops import smooth_mesh
+        v = smooth_mesh(v, t, iterations=smooth, lam=smooth_lambda, mu=smooth_mu, pin="boundary")
     vi = v
     if coords == "unit":
         v = v / res - .5
@@ -365,19 +374,24 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
 
 @torch.no_grad()
 def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, res=255, threshold=10.,
-                normals=False, colors=False, view="normal", keep_largest=None, min_triangles=0):
+                normals=False, colors=False, view="normal", keep_largest=None, min_triangles=0, smooth=0,
+                smooth_lambda=0.5, smooth_mu=-0.53):
     """Drop-in for run_render.render_mesh (run_render.py:970-986): per pose, the density grid and its iso-surface
     on the device, written to basedir/meshes/{i:03d}.ply in the reference's vertices / res - .5 coordinates.
     Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it).
     `normals` / `colors` / `view`: as RayCaster.extract_mesh; the attributes go into the PLYs (nx / ny / nz,
     red / green / blue) and the list holds (vertices, triangles, attrs).  `keep_largest` / `min_triangles`: the
-    component filter of RayCaster.extract_mesh (keep_largest=1: the body without floaters)."""
+    component filter of RayCaster.extract_mesh (keep_largest=1: the body without floaters).  `smooth` /
+    `smooth_lambda` / `smooth_mu`: its Taubin smoothing, after the filter; the PLYs hold the smoothed vertices, and
+    their normals stay the gradient normals of the unsmoothed crossing."""
     ray_caster = render_kwargs["ray_caster"]
     os.makedirs(os.path.join(basedir, "meshes"), exist_ok=True)
     kps, skts, bones = tensor_data["kp"], tensor_data["skts"], tensor_data["bones"]
     extras = dict(normals=normals, colors=colors, view=view) if (normals or colors) else {}
     keeps = (dict(keep_largest=keep_largest, min_triangles=min_triangles)
              if (keep_largest is not None or min_triangles > 0) else {})
+    if smooth != 0:
+        keeps.update(smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
     v_t_tuples = []
     for i in range(len(kps)):
         out = ray_caster.extract_mesh(kps[i:i + 1], skts[i:i + 1], None if bones is None else bones[i:i + 1],

@@ -1,4 +1,4 @@
-"""Connected components of an extracted mesh and floater removal, on the device.
+"""Connected components of an extracted mesh and floater removal, its vertex adjacency and smoothing, on the device.
 
 The iso-surface of a noisy density (isosurface.py) is the body plus detached blobs of density ("floaters") and closed
 cavity surfaces inside it.  The reference leaves them to the user (trimesh, split(), keep the biggest: a trip to the
@@ -16,6 +16,23 @@ checkers, reached only by those names -- nothing falls back to them):
   * filtering keeps a component iff rank < keep_largest (when given) and triangle_count >= min_triangles; a vertex
     survives iff its component does, a triangle iff its three vertices do; the surviving vertices and triangles
     keep their original relative order, ids remapped; every per-vertex array is gathered with the same index.
+
+The surface that remains is a noisy density's: voxel staircases and ripple, which the reference's users smooth on the
+host (trimesh.smoothing.filter_taubin).  `vertex_adjacency` builds the vertex connectivity as a CSR
+(anerf_mesh_adjacency_count, anerf_mesh_adjacency_emit) and `smooth_mesh` runs Laplacian / Taubin steps over it
+(anerf_mesh_smooth: one gather kernel, launched once per step).  Their contract, shared with
+`vertex_adjacency_reference` / `smooth_mesh_reference` (NumPy checkers again, reached only by those names):
+  * every triangle (a, b, c) lists the ordered pairs (a,b) (a,c) (b,a) (b,c) (c,a) (c,b); pairs with equal ends are
+    dropped; row v is the set of distinct u with (v,u) listed, ascending (offsets int32 [V + 1], neighbors int32 [E]);
+    a vertex that no triangle uses has an empty row;
+  * boundary[v] iff some (v,u) is listed exactly once; a duplicated triangle, or a degenerate one such as (1,1,3),
+    lists its pairs twice, which is not boundary.  Integers only: the same on every run;
+  * one smoothing step with weight w, for a vertex v with neighbours u_0 < ... < u_{d-1}, d > 0, not pinned, per
+    component in fp32 with every operation separately rounded: s = p[u_0], then s = s + p[u_k] for k = 1 .. d-1 in that
+    order; m = s / float(d); p'[v] = p[v] + w (m - p[v]).  d = 0 or pinned: p'[v] = p[v], bit for bit.  Every step
+    reads only the previous step's positions (Jacobi).  NaN and inf propagate as the arithmetic gives them;
+  * one iteration is a step with lam, then a step with mu when mu is given (Taubin's lambda | mu, which does not
+    shrink the body as the plain Laplacian does).
 """
 import collections
 
@@ -25,6 +42,7 @@ import torch
 from . import _lib
 
 MeshComponents = collections.namedtuple("MeshComponents", ["labels", "roots", "triangle_counts", "vertex_counts"])
+VertexAdjacency = collections.namedtuple("VertexAdjacency", ["offsets", "neighbors", "boundary"])
 
 
 def _check_ids(triangles, n_vertices, who):
@@ -238,3 +256,177 @@ def filter_mesh_reference(vertices, triangles, attrs=None, keep_largest=None, mi
     out_t = vertex_map[tri[alive]].astype(np.int32).reshape(-1, 3)
     out_a = _gather_attrs(attrs, lambda a: host(a)[kept], len(v))
     return (v[kept], out_t) if attrs is None else (v[kept], out_t, out_a)
+
+
+# ------------------------------------------------------------------ vertex adjacency and smoothing
+def _adjacency(t, n_vertices):
+    """anerf_mesh_adjacency_count / _emit on a checked device list."""
+    dev = t.device
+    lib = _lib.load()
+    nv, nt = int(n_vertices), int(t.shape[0])
+    if 6 * nt >= 2 ** 31:
+        raise ValueError(f"vertex_adjacency: {nt} triangles list {6 * nt} pairs, which do not fit int32 offsets")
+    with torch.cuda.device(dev):
+        stream = _lib.stream_handle(dev)
+        need = lib.anerf_mesh_adjacency_workspace(nv, nt)
+        if need == 0:
+            raise _lib.AnerfError(f"anerf_mesh_adjacency_workspace: {lib.anerf_last_error().decode(errors='replace')}")
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        offsets = torch.empty(nv + 1, device=dev, dtype=torch.int32)
+        boundary = torch.empty(nv, device=dev, dtype=torch.uint8)
+        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        _lib.check(lib.anerf_mesh_adjacency_count(_lib.ptr(t), nt, nv, _lib.ptr(ws), need, _lib.ptr(offsets),
+                                                  _lib.ptr(boundary), _lib.ptr(totals), stream),
+                   "anerf_mesh_adjacency_count")
+        ne = int(totals.cpu()[0])  # (the one sync: the number of entries)
+        neighbors = torch.empty(ne, device=dev, dtype=torch.int32)
+        _lib.check(lib.anerf_mesh_adjacency_emit(nv, _lib.ptr(ws), need, _lib.ptr(offsets), _lib.ptr(neighbors), ne,
+                                                 stream), "anerf_mesh_adjacency_emit")
+    return VertexAdjacency(offsets, neighbors, boundary.view(torch.bool))  # (the kernels write 0 / 1)
+
+
+@torch.no_grad()
+def vertex_adjacency(triangles, n_vertices):
+    """The vertex adjacency of the mesh (triangles int [T, 3], ids in [0, n_vertices)) as a CSR of device tensors:
+      offsets int32 [V + 1], neighbors int32 [E]   row v, neighbors[offsets[v]:offsets[v + 1]], holds the distinct
+                                                   vertices that share a triangle edge with v, ascending;
+      boundary bool [V]                            v is on an edge that only one triangle has (module docstring).
+    An id outside [0, n_vertices) raises ValueError before anything is launched, and so do 6 T >= 2^31 listed pairs.
+    One host read of E sits between the count and the emit launches (as in compact_mesh); everything runs on the
+    current stream."""
+    return _adjacency(_device_triangles(triangles, n_vertices, "vertex_adjacency"), int(n_vertices))
+
+
+def _listed_pairs(tri):
+    """The ordered pairs the triangles list, equal ends dropped: (first ends, second ends), int64."""
+    a, b = tri[:, [0, 0, 1, 1, 2, 2]].reshape(-1), tri[:, [1, 2, 0, 2, 0, 1]].reshape(-1)
+    ok = a != b
+    return a[ok], b[ok]
+
+
+def vertex_adjacency_reference(triangles, n_vertices):
+    """NumPy implementation of the adjacency's contract, the checker of `vertex_adjacency`: the listed pairs as
+    sorted keys v * V + u, their distinct values and multiplicities.  Returns VertexAdjacency of arrays."""
+    if isinstance(triangles, torch.Tensor):
+        triangles = triangles.detach().cpu().numpy()
+    tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    nv = int(n_vertices)
+    if len(tri) and (tri.min() < 0 or tri.max() >= nv):
+        raise ValueError(f"vertex_adjacency_reference: vertex ids span [{tri.min()}, {tri.max()}], outside [0, {nv})")
+    if 6 * len(tri) >= 2 ** 31:
+        raise ValueError(f"vertex_adjacency_reference: {len(tri)} triangles list too many pairs for int32 offsets")
+    a, b = _listed_pairs(tri)
+    keys, mult = np.unique(a * max(nv, 1) + b, return_counts=True)
+    v, u = keys // max(nv, 1), keys % max(nv, 1)
+    offsets = np.zeros(nv + 1, np.int64)
+    np.cumsum(np.bincount(v, minlength=nv), out=offsets[1:])
+    boundary = np.zeros(nv, bool)
+    boundary[v[mult == 1]] = True
+    return VertexAdjacency(offsets.astype(np.int32), u.astype(np.int32), boundary)
+
+
+def _smooth_args(shape, iterations, lam, mu, who):
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{who}: vertices must be [V, 3], got shape {tuple(shape)}")
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f"{who}: iterations must be an integer >= 0, got {iterations}")
+    if not np.isfinite(lam) or (mu is not None and not np.isfinite(mu)):
+        raise ValueError(f"{who}: lam and mu must be finite, got {lam}, {mu}")
+
+
+def _pin_mask(pin, n_vertices, boundary, who):
+    """`pin` as None or a [V] mask: "boundary" -> boundary() (evaluated only then), None, or the caller's mask."""
+    if pin is None:
+        return None
+    if isinstance(pin, str):
+        if pin != "boundary":
+            raise ValueError(f"{who}: pin must be 'boundary', None or a mask [V], got {pin!r}")
+        return boundary()
+    shape = tuple(pin.shape)
+    if shape != (n_vertices,):
+        raise ValueError(f"{who}: the pin mask has shape {shape} for {n_vertices} vertices")
+    return pin
+
+
+@torch.no_grad()
+def smooth_mesh(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, pin="boundary", adjacency=None):
+    """Laplacian / Taubin smoothing of a mesh (vertices float [V, 3], triangles int [T, 3]) on the device: every
+    iteration moves each vertex towards the mean of its neighbours by `lam`, then by `mu` (negative: back out, so
+    that the body keeps its volume -- Taubin's lambda | mu); mu=None gives the plain Laplacian, which shrinks.
+    Returns the positions float32 [V, 3] on the device; the input is not written.  The arithmetic is the module
+    docstring's contract, bit for bit the same as `smooth_mesh_reference`.
+    `pin`: "boundary" holds the vertices of open edges in place (a body cut open by the grid box does not shrink
+    from its rim), None pins nothing, or a bool / uint8 mask [V] of vertices to hold.
+    `adjacency`: a VertexAdjacency of the same mesh from `vertex_adjacency` to reuse (the triangles are not read
+    then); otherwise it is built here, with its one host read.
+    iterations=0 returns `vertices` as given and launches nothing.  Every step is one launch of anerf_mesh_smooth's
+    kernel on the current stream."""
+    shape = tuple(vertices.shape) if hasattr(vertices, "shape") else np.shape(vertices)
+    _smooth_args(shape, iterations, lam, mu, "smooth_mesh")
+    if not isinstance(pin, str) and pin is not None:
+        pin = torch.as_tensor(pin)
+    _pin_mask(pin, shape[0], lambda: None, "smooth_mesh")  # (the argument errors come before any launch)
+    if int(iterations) == 0:
+        return vertices
+    nv = shape[0]
+    adj = adjacency if adjacency is not None else vertex_adjacency(triangles, nv)
+    if tuple(adj.offsets.shape) != (nv + 1,):
+        raise ValueError(f"smooth_mesh: the adjacency has {adj.offsets.shape[0] - 1} rows for {nv} vertices")
+    dev = adj.offsets.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        p = torch.as_tensor(vertices).to(dev, torch.float32).contiguous()
+        mask = _pin_mask(pin, nv, lambda: adj.boundary, "smooth_mesh")
+        if mask is not None:
+            mask = mask.to(dev).ne(0).to(torch.uint8).contiguous()
+        out = torch.empty_like(p)
+        scratch = torch.empty_like(p)
+        flags = _lib.ANERF_SMOOTH_TAUBIN if mu is not None else 0
+        _lib.check(lib.anerf_mesh_smooth(_lib.ptr(p), nv, _lib.ptr(adj.offsets), _lib.ptr(adj.neighbors),
+                                         int(adj.neighbors.shape[0]), _lib.ptr(mask), int(iterations), float(lam),
+                                         float(mu) if mu is not None else 0.0, flags, _lib.ptr(out),
+                                         _lib.ptr(scratch), _lib.stream_handle(dev)), "anerf_mesh_smooth")
+    return out
+
+
+def _smooth_step_reference(p, offsets, neighbors, w, pinned):
+    """One step of the contract on float32 [V, 3]: the row sums taken column by column (k = 0, 1, ...: the k-th
+    neighbour of every row that has one), which keeps each row's order of additions."""
+    deg = np.diff(offsets)
+    start = offsets[:-1]
+    s = np.zeros_like(p)
+    for k in range(int(deg.max()) if len(deg) else 0):
+        rows = np.nonzero(deg > k)[0]
+        q = p[neighbors[start[rows] + k]]
+        s[rows] = q if k == 0 else s[rows] + q
+    out = p.copy()
+    move = np.nonzero((deg > 0) & ~pinned)[0]
+    with np.errstate(all="ignore"):
+        m = s[move] / deg[move].astype(np.float32)[:, None]
+        out[move] = p[move] + np.float32(w) * (m - p[move])
+    return out
+
+
+def smooth_mesh_reference(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, pin="boundary", adjacency=None):
+    """NumPy implementation of `smooth_mesh`'s contract on `vertex_adjacency_reference`: its checker.  float32
+    throughout; returns an array [V, 3]."""
+    def host(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    v = host(vertices)
+    _smooth_args(v.shape, iterations, lam, mu, "smooth_mesh_reference")
+    p = np.array(v, dtype=np.float32)
+    nv = len(p)
+    if not isinstance(pin, str) and pin is not None:
+        pin = host(pin)
+    _pin_mask(pin, nv, lambda: None, "smooth_mesh_reference")
+    if int(iterations) == 0:
+        return p
+    adj = adjacency if adjacency is not None else vertex_adjacency_reference(triangles, nv)
+    mask = _pin_mask(pin, nv, lambda: host(adj.boundary), "smooth_mesh_reference")
+    pinned = np.zeros(nv, bool) if mask is None else mask != 0
+    offsets, neighbors = host(adj.offsets).astype(np.int64), host(adj.neighbors).astype(np.int64)
+    for _ in range(int(iterations)):
+        p = _smooth_step_reference(p, offsets, neighbors, lam, pinned)
+        if mu is not None:
+            p = _smooth_step_reference(p, offsets, neighbors, mu, pinned)
+    return p

@@ -28,6 +28,8 @@
  *                           viewer accumulates face normals on the host)       render_mesh.py:35-53
  *   anerf_mesh_components,  the connected components of that mesh and its stable compaction (ABI 22; the reference
  *   anerf_mesh_compact_*    leaves floaters and cavities to the user: trimesh's split() on the host)
+ *   anerf_mesh_adjacency_*, the vertex adjacency of that mesh as a CSR and Laplacian / Taubin smoothing over it (ABI 23;
+ *   anerf_mesh_smooth       the reference leaves smoothing to the user: trimesh.smoothing.filter_taubin on the host)
  *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
  *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
@@ -71,7 +73,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 22
+#define ANERF_ABI_VERSION 23
 
 enum {
     ANERF_OK = 0,
@@ -427,6 +429,52 @@ int anerf_mesh_compact_count(const uint8_t* keep, int64_t n_vertices, const int3
 int anerf_mesh_compact_emit(const uint8_t* keep, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
                             const void* ws, size_t ws_bytes, int32_t* vertex_map, int32_t* kept, int64_t max_kept,
                             int32_t* triangles_out, int64_t max_triangles, void* stream);
+
+/* ABI 23: the vertex adjacency of such a mesh as a CSR.  Every triangle (a, b, c) lists the ordered pairs (a,b) (a,c)
+ * (b,a) (b,c) (c,a) (c,b); pairs with equal ends are dropped.  Row v is the set of distinct u with (v,u) listed,
+ * ascending; a vertex no triangle uses has an empty row:
+ *   offsets [n_vertices + 1]   row v is neighbors[offsets[v] .. offsets[v + 1]);
+ *   neighbors [E]              the rows, one after the other;
+ *   boundary [n_vertices]      1 iff some (v,u) is listed exactly once (an edge with one triangle on it), else 0: a
+ *                              duplicated triangle, or a degenerate one such as (1,1,3), lists its pairs twice.
+ * All outputs are integers and the same on every run.  anerf_mesh_adjacency_count writes offsets, boundary and
+ * totals_dev (device, int64 [2]: E, the largest distinct degree) and leaves the sorted rows in ws; the caller reads
+ * E (the one synchronisation), allocates, and calls anerf_mesh_adjacency_emit with the SAME n_vertices, ws and
+ * offsets.  max_neighbors is the capacity in entries (in [0, 2^31); neighbors may be NULL where it is 0): no store
+ * goes past it, entries beyond it are dropped.  Rows are counted and filled with integer atomics, sorted (a row of
+ * up to 64 listed pairs by one thread, a longer one by a workgroup's bitonic network) and their distinct entries
+ * taken from the runs; no kernel waits for another workgroup.  Precondition: ids lie in [0, n_vertices); a triangle
+ * with an id outside is skipped by every kernel, so a bad list cannot write out of bounds.  n_tri == 0 and
+ * n_vertices == 0 are valid (triangles and boundary may be NULL where their extent is 0; offsets[0] is written
+ * always).  ws: anerf_mesh_adjacency_workspace(n_vertices, n_tri) bytes, 4-byte aligned (never 0 for valid counts;
+ * 0, with a message, for n_vertices outside [0, 2^31) or 6 n_tri >= 2^31).  Allocation-free, asynchronous on `stream`.
+ * ANERF_EINVAL, before any HIP call, for such counts, a capacity outside [0, 2^31), a NULL pointer with a non-zero
+ * extent, a NULL or misaligned or short workspace (emit can only tell that the part before the rows is missing: it
+ * never reads past ws_bytes). */
+size_t anerf_mesh_adjacency_workspace(int64_t n_vertices, int64_t n_tri);
+int anerf_mesh_adjacency_count(const int32_t* triangles, int64_t n_tri, int64_t n_vertices, void* ws, size_t ws_bytes,
+                               int32_t* offsets, uint8_t* boundary, int64_t* totals_dev, void* stream);
+int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, const int32_t* offsets, int32_t* neighbors,
+                              int64_t max_neighbors, void* stream);
+
+/* ABI 23: Laplacian / Taubin smoothing of positions [n_vertices][3] over such a CSR (n_neighbors: its E).  One step
+ * with weight w, for a vertex v with neighbours u_0 < u_1 < ... < u_{d-1} (its row), d > 0, not pinned, per
+ * component, fp32, every operation separately rounded:
+ *   s = p[u_0], then s = s + p[u_k] for k = 1 .. d-1 in that order; m = s / (float)d; p'[v] = p[v] + w (m - p[v]);
+ * with d == 0 or pinned[v] != 0, p'[v] = p[v] bit for bit.  Every step reads only the previous step's positions
+ * (Jacobi, two buffers) and is one launch: a step needs every position of the step before, and no kernel waits for
+ * another workgroup.  One iteration is a step with lambda, and under ANERF_SMOOTH_TAUBIN a step with mu after it (mu is
+ * ignored without the flag).  NaN and infinity propagate as the arithmetic gives them.  The result lands in `out`
+ * whatever the number of steps; `scratch` [n_vertices][3] is the other buffer (may be NULL for fewer than two steps);
+ * `positions` is never written.  iterations == 0 copies positions to out.  pinned: uint8 [n_vertices] or NULL (no
+ * vertex pinned).  A bad CSR cannot read out of bounds: a row bound outside [0, n_neighbors] is clamped, a neighbour
+ * id outside [0, n_vertices) is skipped and not counted in d.  Allocation-free, asynchronous on `stream`.
+ * ANERF_EINVAL, before any HIP call, for a count outside [0, 2^31), iterations outside [0, 2^30), unknown flags, a
+ * NULL pointer with a non-zero extent, or positions, out and scratch overlapping one another. */
+enum { ANERF_SMOOTH_TAUBIN = 1 };
+int anerf_mesh_smooth(const float* positions, int64_t n_vertices, const int32_t* offsets, const int32_t* neighbors,
+                      int64_t n_neighbors, const uint8_t* pinned, int32_t iterations, float lambda, float mu,
+                      int32_t flags, float* out, float* scratch, void* stream);
 
 /* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
  * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /

@@ -18,6 +18,14 @@ emit); filter_mesh_ms, filter_mesh(keep_largest=1) on positions and normals -- w
 (extract_mesh_keep_largest_ms is that call).  components_reference_host_ms is mesh_components_reference (NumPy) on
 the same mesh, once, for scale.
 
+Adjacency and smoothing (meshops.py), on the body that keep_largest=1 leaves: adjacency_ms, meshops.vertex_adjacency
+whole (the id range check, the kernels, the host read of E); adjacency_kernels_ms, the launches of
+anerf_mesh_adjacency_count and _emit back to back into preallocated outputs; smooth_ms, smooth_mesh at its defaults
+(10 Taubin iterations: 20 launches) on a precomputed adjacency; smooth_step_us, one launch of the step kernel, from the
+difference to a 100-iteration call; extract_mesh_smooth_ms, extract_mesh(keep_largest=1, smooth=10), to put next to
+extract_mesh_keep_largest_ms.  smooth_reference_host_ms is smooth_mesh_reference (NumPy) on the same mesh, once, for
+scale; the device result is checked against it bit for bit.
+
 Prints one JSON line, and appends it to the file given with --append (the record: profiles/mesh_bench.jsonl).
 Usage: python tools/mesh_bench.py [res] [precision] [--append FILE]"""
 import importlib
@@ -105,6 +113,45 @@ def _filter_legs(rc, kps, skts, res, thr, v, t, nrm):
             "extract_mesh_keep_largest_ms": round(keep_ms, 3), "components_reference_host_ms": round(ref_ms, 1)}
 
 
+def _smooth_legs(rc, kps, skts, res, thr, v, t):
+    """Adjacency and smoothing on the body (the mesh keep_largest=1 leaves), in index coordinates."""
+    _lib = importlib.import_module("a-nerf_amd._lib")
+    lib = _lib.load()
+    v, t = meshops.filter_mesh(v, t, keep_largest=1)
+    nv, nt = int(v.shape[0]), int(t.shape[0])
+    adj_ms, adj = _time(lambda: meshops.vertex_adjacency(t, nv), reps=20)
+    ne = int(adj.neighbors.shape[0])
+    need = lib.anerf_mesh_adjacency_workspace(nv, nt)
+    ws = torch.empty(need, device=t.device, dtype=torch.uint8)
+    offsets = torch.empty(nv + 1, device=t.device, dtype=torch.int32)
+    boundary = torch.empty(nv, device=t.device, dtype=torch.uint8)
+    neighbors = torch.empty(ne, device=t.device, dtype=torch.int32)
+    totals = torch.empty(2, device=t.device, dtype=torch.int64)
+
+    def kernels():  # both entries back to back, no host read
+        s = _lib.stream_handle(t.device)
+        _lib.check(lib.anerf_mesh_adjacency_count(_lib.ptr(t), nt, nv, _lib.ptr(ws), need, _lib.ptr(offsets),
+                                                  _lib.ptr(boundary), _lib.ptr(totals), s), "anerf_mesh_adjacency_count")
+        _lib.check(lib.anerf_mesh_adjacency_emit(nv, _lib.ptr(ws), need, _lib.ptr(offsets), _lib.ptr(neighbors), ne, s),
+                   "anerf_mesh_adjacency_emit")
+    adj_kernels_ms, _ = _time(kernels, reps=20)
+    assert torch.equal(neighbors, adj.neighbors) and torch.equal(offsets, adj.offsets)
+    smooth_ms, sm = _time(lambda: meshops.smooth_mesh(v, t, adjacency=adj), reps=20)  # 10 Taubin iterations
+    long_ms, _ = _time(lambda: meshops.smooth_mesh(v, t, iterations=100, adjacency=adj), reps=5)
+    step_us = (long_ms - smooth_ms) / 180.0 * 1e3  # (the calls differ by 180 launches of the step kernel)
+    extract_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, keep_largest=1,
+                                                  smooth=10))
+    v_host, t_host = v.cpu().numpy(), t.cpu().numpy()
+    t0 = time.perf_counter()
+    ref = meshops.smooth_mesh_reference(v_host, t_host)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    assert np.array_equal(ref.view(np.int32), sm.cpu().numpy().view(np.int32))
+    return {"adjacency_entries": ne, "largest_degree": int(totals[1]), "boundary_vertices": int(adj.boundary.sum()),
+            "adjacency_ms": round(adj_ms, 3), "adjacency_kernels_ms": round(adj_kernels_ms, 3),
+            "smooth_ms": round(smooth_ms, 3), "smooth_step_us": round(step_us, 2),
+            "extract_mesh_smooth_ms": round(extract_ms, 3), "smooth_reference_host_ms": round(ref_ms, 1)}
+
+
 def main():
     argv = list(sys.argv[1:])
     append = None
@@ -131,6 +178,7 @@ def main():
                                                 colors=True))
     _, ti, ni = iso.isosurface(grid, thr, relu=True, normals=True)
     legs = _filter_legs(rc, kps, skts, res, thr, v, ti, ni)
+    legs.update(_smooth_legs(rc, kps, skts, res, thr, v, ti))
     n = (res + 1) ** 3
     line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
                       "grid_ms": round(grid_ms, 3), "isosurface_ms": round(iso_ms, 3),
