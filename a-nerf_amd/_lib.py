@@ -8,7 +8,8 @@ missing this module raises.
 import ctypes
 import os
 
-import torch  # noqa: F401  (must be loaded before the HIP library, see module docstring)
+import numpy as np
+import torch  # (must be loaded before the HIP library, see module docstring)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libanerf_hip.so")  # (the in-tree build; the package reads no environment)
@@ -358,6 +359,20 @@ def check(rc, what):
     if rc != 0:
         msg = load().anerf_last_error().decode(errors="replace")
         raise AnerfError(f"{what} failed ({rc}): {msg}")
+
+
+def workspace(name, *args):
+    """The bytes the `*_workspace` entry `name` asks for; a 0 is its refusal, raised with anerf_last_error()."""
+    lib = load()
+    need = getattr(lib, name)(*args)
+    if need == 0:
+        raise AnerfError(f"{name}: {lib.anerf_last_error().decode(errors='replace')}")
+    return need
+
+
+def host_array(x):
+    """A tensor (any device) or array-like as a NumPy array."""
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
 def ptr(t):

@@ -5,9 +5,10 @@ include/anerf.h is stored next to the library (`libanerf_hip.so.stamp`).  A ship
 stamp does not match the sources is rebuilt, never reused because of its mtime.
 
 The translation units compile in parallel into objects cached under `.objs/` by the hash of
-their own dependencies (anerf_gemm.hip and anerf_mesh.hip read only include/anerf.h, anerf_iso.hip its case
-table and include/anerf.h), then link into the library: an edit of the training GEMMs, of the iso-surface or
-of the mesh kernels recompiles one unit, not the render kernels' instances.
+their own dependencies (anerf_gemm.hip reads only include/anerf.h; anerf_iso.hip and anerf_mesh.hip that and
+csrc/anerf_scan.hpp, which no other unit reads, anerf_iso.hip also its case table), then link into the library: an
+edit of the training GEMMs, of the iso-surface or of the mesh kernels recompiles one unit, an edit of their shared
+scan header those two, never the render kernels' instances.
 """
 import hashlib
 import os
@@ -20,6 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "anerf.h")
 SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_gemm.hip"),
        os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip")]
+SCAN_HEADER = os.path.join(CSRC, "anerf_scan.hpp")  # anerf_iso.hip's and anerf_mesh.hip's alone
 OUT = os.path.join(HERE, "libanerf_hip.so")
 STAMP = OUT + ".stamp"
 OBJS = os.path.join(HERE, ".objs")
@@ -48,13 +50,17 @@ def source_hash():
 
 
 def unit_deps(src):
-    """The files a translation unit reads: anerf_gemm.hip and anerf_mesh.hip only the C header, anerf_iso.hip its
-    case table and the C header, anerf_render.hip every csrc header."""
-    if os.path.basename(src) in ("anerf_gemm.hip", "anerf_mesh.hip"):
+    """The files a translation unit reads: anerf_gemm.hip only the C header; anerf_mesh.hip and anerf_iso.hip the
+    scan header and the C header, anerf_iso.hip its case table as well; anerf_render.hip every other csrc header."""
+    name = os.path.basename(src)
+    if name == "anerf_gemm.hip":
         return [src, HEADER]
-    if os.path.basename(src) == "anerf_iso.hip":
-        return [src, os.path.join(CSRC, "anerf_iso_table.inc"), HEADER]
-    return [src] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")) + [HEADER]
+    if name == "anerf_mesh.hip":
+        return [src, SCAN_HEADER, HEADER]
+    if name == "anerf_iso.hip":
+        return [src, os.path.join(CSRC, "anerf_iso_table.inc"), SCAN_HEADER, HEADER]
+    return [src] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
+                          if f.endswith(".hpp") and f != os.path.basename(SCAN_HEADER)) + [HEADER]
 
 
 def stamp_matches():

@@ -22,26 +22,18 @@
 // emit passes can never produce more than the count pass counted; all output stores are guarded by the
 // capacities passed in all the same.
 //
-// A workgroup is 256 threads x 4 consecutive points (consecutive in the grid's last axis, so a wave reads 1 KB
-// runs); the neighbour rows a cell needs (+1 in axis 0 / 1) are read through the cache.  The pass is bound by
-// those reads (4 B per point per pass) and the 4 B per point of first-vertex ids.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-
-#include "../../include/anerf.h"
-
-int anerf_internal_fail(int code, const char* msg);  // anerf_render.hip: sets anerf_last_error()
+// The tiles, the block scan, scan_kernel, the base | counts head of the workspace and the host helpers are
+// anerf_scan.hpp's, shared with anerf_mesh.hip.  A workgroup is 256 threads x 4 consecutive points (consecutive in
+// the grid's last axis, so a wave reads 1 KB runs); the neighbour rows a cell needs (+1 in axis 0 / 1) are read
+// through the cache.  The pass is bound by those reads (4 B per point per pass) and the 4 B per point of
+// first-vertex ids.
+#include "anerf_scan.hpp"
 
 namespace {
 
 #define ANERF_ISO_QUAL __device__ const
 #include "anerf_iso_table.inc"
 
-constexpr int NTHR = 256;               // threads per workgroup
-constexpr int ITEMS = 4;                // consecutive points per thread
-constexpr int TILE = NTHR * ITEMS;      // points per workgroup
 constexpr int ISO_FLAGS = ANERF_ISO_RELU | ANERF_ISO_FLIP;
 
 struct Grid {
@@ -109,24 +101,6 @@ __device__ __forceinline__ int lower_axis_crossings(const Grid& g, int q, int ax
     return cnt;
 }
 
-// Exclusive scan of one int per thread over the workgroup (NTHR threads); `total` is the workgroup's sum.
-__device__ __forceinline__ int block_exclusive_scan(int x, int* lds, int& total) {
-    const int t = threadIdx.x;
-    __syncthreads();  // (lds may still be read by a previous call)
-    lds[t] = x;
-    __syncthreads();
-    int acc = x;
-    for (int d = 1; d < NTHR; d <<= 1) {
-        const int y = t >= d ? lds[t - d] : 0;
-        __syncthreads();
-        acc += y;
-        lds[t] = acc;
-        __syncthreads();
-    }
-    total = lds[NTHR - 1];
-    return acc - x;
-}
-
 __global__ __launch_bounds__(NTHR) void count_kernel(Grid g, int* __restrict__ block_counts, int nblocks) {
     __shared__ int lds[NTHR];
     const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
@@ -148,36 +122,11 @@ __global__ __launch_bounds__(NTHR) void count_kernel(Grid g, int* __restrict__ b
     }
 }
 
-// One workgroup: base[b] = sum of counts[< b] for the vertex and the triangle counts, tiles of NTHR with a carry.
-__global__ __launch_bounds__(NTHR) void scan_kernel(const int* __restrict__ block_counts, long long* __restrict__ base,
-                                                    int nblocks, long long* __restrict__ totals) {
-    __shared__ int lds[NTHR];
-    long long carry_v = 0, carry_t = 0;
-    for (int start = 0; start < nblocks; start += NTHR) {
-        const int b = start + threadIdx.x;
-        const int cv = b < nblocks ? block_counts[b] : 0;
-        const int ct = b < nblocks ? block_counts[nblocks + b] : 0;
-        int tv, tt;  // (a tile sums at most NTHR * 5 * TILE: fits an int)
-        const int ev = block_exclusive_scan(cv, lds, tv);
-        const int et = block_exclusive_scan(ct, lds, tt);
-        if (b < nblocks) {
-            base[b] = carry_v + ev;
-            base[nblocks + b] = carry_t + et;
-        }
-        carry_v += tv;
-        carry_t += tt;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = carry_v;
-        totals[1] = carry_t;
-    }
-}
-
-__global__ __launch_bounds__(NTHR) void vertex_kernel(Grid g, const long long* __restrict__ base, int* __restrict__ first_id,
-                                                      float* __restrict__ vertices, long long max_vertices) {
-    __shared__ int lds[NTHR];
-    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
-    Point pts[ITEMS];
+// The prologue of the two vertex passes: the thread's ITEMS points from `first` on classified into pts (vmask 0 past
+// the grid's end), their crossing edges counted and scanned over the workgroup.  Returns the thread's first vertex id.
+// (g by value: the kernels then compile to the instructions of the prologue written out in each; by reference not.)
+__device__ __forceinline__ long long classify_tile(Grid g, const long long* base, long long first, Point (&pts)[ITEMS],
+                                                   int* lds) {
     int nv = 0;
     for (int it = 0; it < ITEMS; ++it) {
         pts[it].vmask = 0;
@@ -187,7 +136,15 @@ __global__ __launch_bounds__(NTHR) void vertex_kernel(Grid g, const long long* _
         }
     }
     int total;
-    long long id = base[blockIdx.x] + block_exclusive_scan(nv, lds, total);
+    return base[blockIdx.x] + block_exclusive_scan(nv, lds, total);
+}
+
+__global__ __launch_bounds__(NTHR) void vertex_kernel(Grid g, const long long* __restrict__ base, int* __restrict__ first_id,
+                                                      float* __restrict__ vertices, long long max_vertices) {
+    __shared__ int lds[NTHR];
+    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
+    Point pts[ITEMS];
+    long long id = classify_tile(g, base, first, pts, lds);
     for (int it = 0; it < ITEMS; ++it) {
         if (first + it >= g.n) break;
         const Point& pt = pts[it];
@@ -218,23 +175,14 @@ __device__ __forceinline__ float grad_axis(const Grid& g, int idx, int c, int n,
     return (load(g, idx + st) - load(g, idx - st)) * 0.5f;
 }
 
-// vertex_kernel's classification and scan again (the ids are recomputed, not read: the pass needs the count
-// pass's bases only), writing each vertex's normal instead of its position.
+// vertex_kernel's ids through the same classify_tile (recomputed, not read: the pass needs the count pass's bases
+// only), writing each vertex's normal instead of its position.
 __global__ __launch_bounds__(NTHR) void normal_kernel(Grid g, const long long* __restrict__ base,
                                                       float* __restrict__ normals, long long max_vertices, int flip) {
     __shared__ int lds[NTHR];
     const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
     Point pts[ITEMS];
-    int nv = 0;
-    for (int it = 0; it < ITEMS; ++it) {
-        pts[it].vmask = 0;
-        if (first + it < g.n) {
-            pts[it] = classify(g, (int)(first + it), false);
-            nv += __popc(pts[it].vmask);
-        }
-    }
-    int total;
-    long long id = base[blockIdx.x] + block_exclusive_scan(nv, lds, total);
+    long long id = classify_tile(g, base, first, pts, lds);
     for (int it = 0; it < ITEMS; ++it) {
         if (first + it >= g.n) break;
         const Point& pt = pts[it];
@@ -307,11 +255,11 @@ __global__ __launch_bounds__(NTHR) void triangle_kernel(Grid g, const long long*
     }
 }
 
-// Workspace layout: long long base[2 nblocks] | int block_counts[2 nblocks] | int first_id[n]
+// Workspace layout: the scan's base | block_counts (ScanSpace) | int first_id[n]
 struct Plan {
     long long n;
-    int nblocks;
-    size_t off_counts, off_first, bytes;
+    ScanSpace scan;
+    size_t bytes;  // (first_id starts at scan.bytes)
 };
 
 bool plan(int32_t n0, int32_t n1, int32_t n2, Plan* pl) {
@@ -319,40 +267,25 @@ bool plan(int32_t n0, int32_t n1, int32_t n2, Plan* pl) {
     const long long n = (long long)n0 * n1;  // (< 2^62)
     if (n >= (1ll << 31) || n * n2 >= (1ll << 31)) return false;
     pl->n = n * n2;
-    pl->nblocks = (int)((pl->n + TILE - 1) / TILE);
-    pl->off_counts = (size_t)pl->nblocks * 2 * sizeof(long long);
-    pl->off_first = pl->off_counts + (size_t)pl->nblocks * 2 * sizeof(int);
-    pl->bytes = pl->off_first + (size_t)pl->n * sizeof(int);
+    pl->scan = scan_space(tiles_for(pl->n));
+    pl->bytes = pl->scan.bytes + (size_t)pl->n * sizeof(int);
     return true;
 }
 
+// The checks every entry shares: ANERF_OK and the plan, or the failure as anerf_last_error() has it.
 int check_common(const char* who, const float* grid, int32_t n0, int32_t n1, int32_t n2, int32_t flags, const void* ws,
-                 size_t ws_bytes, Plan* pl, char* msg, size_t msg_len) {
-    if (!grid || !ws) {
-        snprintf(msg, msg_len, "%s: NULL grid or workspace", who);
-        return ANERF_EINVAL;
-    }
-    if (n0 < 1 || n1 < 1 || n2 < 1) {
-        snprintf(msg, msg_len, "%s: grid dimensions %d x %d x %d must be >= 1", who, n0, n1, n2);
-        return ANERF_EINVAL;
-    }
-    if (!plan(n0, n1, n2, pl)) {
-        snprintf(msg, msg_len, "%s: %d x %d x %d grid points do not fit 31 bits", who, n0, n1, n2);
-        return ANERF_EINVAL;
-    }
-    if (flags & ~ISO_FLAGS) {
-        snprintf(msg, msg_len, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ISO_FLAGS));
-        return ANERF_EINVAL;
-    }
-    if ((uintptr_t)ws % 8) {
-        snprintf(msg, msg_len, "%s: the workspace must be 8-byte aligned", who);
-        return ANERF_EINVAL;
-    }
-    if (ws_bytes < pl->bytes) {
-        snprintf(msg, msg_len, "%s: workspace of %zu bytes, %zu needed (anerf_isosurface_workspace)", who, ws_bytes,
-                 pl->bytes);
-        return ANERF_EWORKSPACE;
-    }
+                 size_t ws_bytes, Plan* pl) {
+    if (!grid || !ws) return failf(ANERF_EINVAL, "%s: NULL grid or workspace", who);
+    if (n0 < 1 || n1 < 1 || n2 < 1)
+        return failf(ANERF_EINVAL, "%s: grid dimensions %d x %d x %d must be >= 1", who, n0, n1, n2);
+    if (!plan(n0, n1, n2, pl))
+        return failf(ANERF_EINVAL, "%s: %d x %d x %d grid points do not fit 31 bits", who, n0, n1, n2);
+    if (flags & ~ISO_FLAGS)
+        return failf(ANERF_EINVAL, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ISO_FLAGS));
+    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    if (ws_bytes < pl->bytes)
+        return failf(ANERF_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (anerf_isosurface_workspace)", who,
+                     ws_bytes, pl->bytes);
     return ANERF_OK;
 }
 
@@ -371,14 +304,6 @@ Grid make_grid(const float* grid, int32_t n0, int32_t n1, int32_t n2, const Plan
     return g;
 }
 
-int launched(const char* who) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ANERF_OK;
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(e));
-    return anerf_internal_fail(ANERF_EHIP, msg);
-}
-
 }  // namespace
 
 extern "C" {
@@ -395,16 +320,13 @@ size_t anerf_isosurface_workspace(int32_t n0, int32_t n1, int32_t n2) {
 int anerf_isosurface_count(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags, void* ws,
                            size_t ws_bytes, int64_t* totals_dev, void* stream) {
     Plan pl;
-    char msg[256];
-    const int rc = check_common("anerf_isosurface_count", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
-    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    const int rc = check_common("anerf_isosurface_count", grid, n0, n1, n2, flags, ws, ws_bytes, &pl);
+    if (rc != ANERF_OK) return rc;
     if (!totals_dev) return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_count: NULL totals");
     const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
-    long long* base = (long long*)ws;
-    int* counts = (int*)((char*)ws + pl.off_counts);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(count_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, counts, pl.nblocks);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(NTHR), 0, s, counts, base, pl.nblocks, (long long*)totals_dev);
+    hipLaunchKernelGGL(count_kernel, dim3(pl.scan.nblocks), dim3(NTHR), 0, s, g, pl.scan.counts(ws), pl.scan.nblocks);
+    scan_block_sums(pl.scan, ws, totals_dev, s);
     return launched("anerf_isosurface_count");
 }
 
@@ -412,39 +334,37 @@ int anerf_isosurface_emit(const float* grid, int32_t n0, int32_t n1, int32_t n2,
                           size_t ws_bytes, float* vertices, int64_t max_vertices, int32_t* triangles,
                           int64_t max_triangles, void* stream) {
     Plan pl;
-    char msg[256];
-    const int rc = check_common("anerf_isosurface_emit", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
-    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    const int rc = check_common("anerf_isosurface_emit", grid, n0, n1, n2, flags, ws, ws_bytes, &pl);
+    if (rc != ANERF_OK) return rc;
     if (max_vertices < 0 || max_triangles < 0 || max_vertices > 0x7fffffffll || max_triangles > 0x7fffffffll)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_emit: capacities must be in [0, 2^31)");
     if ((max_vertices > 0 && !vertices) || (max_triangles > 0 && !triangles))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_emit: NULL output with a non-zero capacity");
     const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
     const long long* base = (const long long*)ws;
-    int* first_id = (int*)((char*)ws + pl.off_first);
+    int* first_id = (int*)((char*)ws + pl.scan.bytes);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(vertex_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, base, first_id, vertices,
+    hipLaunchKernelGGL(vertex_kernel, dim3(pl.scan.nblocks), dim3(NTHR), 0, s, g, base, first_id, vertices,
                        (long long)max_vertices);
     if (max_triangles > 0)
-        hipLaunchKernelGGL(triangle_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, g, base + pl.nblocks, first_id, triangles,
-                           (long long)max_triangles, (flags & ANERF_ISO_FLIP) ? 1 : 0);
+        hipLaunchKernelGGL(triangle_kernel, dim3(pl.scan.nblocks), dim3(NTHR), 0, s, g, base + pl.scan.nblocks, first_id,
+                           triangles, (long long)max_triangles, (flags & ANERF_ISO_FLIP) ? 1 : 0);
     return launched("anerf_isosurface_emit");
 }
 
 int anerf_isosurface_normals(const float* grid, int32_t n0, int32_t n1, int32_t n2, float threshold, int32_t flags,
                              const void* ws, size_t ws_bytes, float* normals, int64_t max_vertices, void* stream) {
     Plan pl;
-    char msg[256];
-    const int rc = check_common("anerf_isosurface_normals", grid, n0, n1, n2, flags, ws, ws_bytes, &pl, msg, sizeof msg);
-    if (rc != ANERF_OK) return anerf_internal_fail(rc, msg);
+    const int rc = check_common("anerf_isosurface_normals", grid, n0, n1, n2, flags, ws, ws_bytes, &pl);
+    if (rc != ANERF_OK) return rc;
     if (max_vertices < 0 || max_vertices > 0x7fffffffll)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_normals: the capacity must be in [0, 2^31)");
     if (max_vertices > 0 && !normals)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_isosurface_normals: NULL output with a non-zero capacity");
     if (max_vertices == 0) return ANERF_OK;
     const Grid g = make_grid(grid, n0, n1, n2, pl, threshold, flags);
-    hipLaunchKernelGGL(normal_kernel, dim3(pl.nblocks), dim3(NTHR), 0, (hipStream_t)stream, g, (const long long*)ws,
-                       normals, (long long)max_vertices, (flags & ANERF_ISO_FLIP) ? 1 : 0);
+    hipLaunchKernelGGL(normal_kernel, dim3(pl.scan.nblocks), dim3(NTHR), 0, (hipStream_t)stream, g,
+                       (const long long*)ws, normals, (long long)max_vertices, (flags & ANERF_ISO_FLIP) ? 1 : 0);
     return launched("anerf_isosurface_normals");
 }
 

@@ -46,23 +46,14 @@
 // whatever the schedule: the outputs are deterministic (the tallies are integer atomics).
 //
 // Compaction keeps both outputs in their original relative order: count -> scan -> emit without atomics, the
-// pattern of anerf_iso.hip (256 threads x 4 consecutive items per workgroup).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-
-#include "../../include/anerf.h"
-
-int anerf_internal_fail(int code, const char* msg);  // anerf_render.hip: sets anerf_last_error()
+// pattern of anerf_scan.hpp (256 threads x 4 consecutive items per workgroup), whose tiles, block scan, scan_kernel,
+// workspace layout and host helpers this unit shares with anerf_iso.hip.
+#include "anerf_scan.hpp"
 
 namespace {
 
-constexpr int NTHR = 256;           // threads per workgroup (4 waves of 64)
-constexpr int TALLY_THR = 1024;     // threads per workgroup of the two tallying kernels
+constexpr int TALLY_THR = 1024;  // threads per workgroup of the two tallying kernels
 constexpr int TALLY_WAVES = TALLY_THR / 64;
-constexpr int ITEMS = 4;            // consecutive items per thread (compaction)
-constexpr int TILE = NTHR * ITEMS;  // items per workgroup (compaction)
 constexpr long long MAXN = 0x7fffffffll;
 
 __device__ __forceinline__ int ld_parent(const int* p) {
@@ -240,24 +231,6 @@ __device__ __forceinline__ bool triangle_kept(const Lists& l, long long p) {
     return l.keep[a] != 0 && l.keep[b] != 0 && l.keep[c] != 0;
 }
 
-// Exclusive scan of one int per thread over the workgroup (NTHR threads); `total` is the workgroup's sum.
-__device__ __forceinline__ int block_exclusive_scan(int x, int* lds, int& total) {
-    const int t = threadIdx.x;
-    __syncthreads();  // (lds may still be read by a previous call)
-    lds[t] = x;
-    __syncthreads();
-    int acc = x;
-    for (int d = 1; d < NTHR; d <<= 1) {
-        const int y = t >= d ? lds[t - d] : 0;
-        __syncthreads();
-        acc += y;
-        lds[t] = acc;
-        __syncthreads();
-    }
-    total = lds[NTHR - 1];
-    return acc - x;
-}
-
 __global__ __launch_bounds__(NTHR) void count_kernel(Lists l, int* __restrict__ block_counts, int nblocks) {
     __shared__ int lds[NTHR];
     const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
@@ -272,31 +245,6 @@ __global__ __launch_bounds__(NTHR) void count_kernel(Lists l, int* __restrict__ 
     if (threadIdx.x == 0) {
         block_counts[blockIdx.x] = tv;
         block_counts[nblocks + blockIdx.x] = tt;
-    }
-}
-
-// One workgroup: base[b] = sum of counts[< b] for the vertex and the triangle counts, tiles of NTHR with a carry.
-__global__ __launch_bounds__(NTHR) void scan_kernel(const int* __restrict__ block_counts, long long* __restrict__ base,
-                                                    int nblocks, long long* __restrict__ totals) {
-    __shared__ int lds[NTHR];
-    long long carry_v = 0, carry_t = 0;
-    for (int start = 0; start < nblocks; start += NTHR) {
-        const int b = start + threadIdx.x;
-        const int cv = b < nblocks ? block_counts[b] : 0;
-        const int ct = b < nblocks ? block_counts[nblocks + b] : 0;
-        int tv, tt;  // (a tile sums at most NTHR * TILE: fits an int)
-        const int ev = block_exclusive_scan(cv, lds, tv);
-        const int et = block_exclusive_scan(ct, lds, tt);
-        if (b < nblocks) {
-            base[b] = carry_v + ev;
-            base[nblocks + b] = carry_t + et;
-        }
-        carry_v += tv;
-        carry_t += tt;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = carry_v;
-        totals[1] = carry_t;
     }
 }
 
@@ -350,55 +298,27 @@ __global__ __launch_bounds__(NTHR) void triangle_kernel(Lists l, const long long
     }
 }
 
-// Workspace of the compaction: long long base[2 nblocks] | int block_counts[2 nblocks]
-struct Plan {
-    int nblocks;
-    size_t off_counts, bytes;
-};
-
-bool plan(int64_t nv, int64_t nt, Plan* pl) {
+// The compaction's workspace is the scan's base | block_counts and nothing more: its plan is the ScanSpace.
+bool plan(int64_t nv, int64_t nt, ScanSpace* pl) {
     if (nv < 0 || nt < 0 || nv > MAXN || nt > MAXN) return false;
-    const long long n = nv > nt ? nv : nt;
-    pl->nblocks = (int)((n + TILE - 1) / TILE);
-    if (pl->nblocks < 1) pl->nblocks = 1;  // (empty lists still get their totals written)
-    pl->off_counts = (size_t)pl->nblocks * 2 * sizeof(long long);
-    pl->bytes = pl->off_counts + (size_t)pl->nblocks * 2 * sizeof(int);
+    const int nblocks = tiles_for(nv > nt ? nv : nt);
+    *pl = scan_space(nblocks < 1 ? 1 : nblocks);  // (empty lists still get their totals written)
     return true;
 }
 
 int check_compact(const char* who, const uint8_t* keep, int64_t nv, const int32_t* tri, int64_t nt, const void* ws,
-                  size_t ws_bytes, Plan* pl) {
-    char msg[256];
-    if (!plan(nv, nt, pl)) {
-        snprintf(msg, sizeof msg, "%s: n_vertices %lld / n_tri %lld must be in [0, 2^31)", who, (long long)nv,
-                 (long long)nt);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
-    if ((nv > 0 && !keep) || (nt > 0 && !tri) || !ws) {
-        snprintf(msg, sizeof msg, "%s: NULL keep, triangles or workspace", who);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
-    if ((uintptr_t)ws % 8) {
-        snprintf(msg, sizeof msg, "%s: the workspace must be 8-byte aligned", who);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
-    if (ws_bytes < pl->bytes) {
-        snprintf(msg, sizeof msg, "%s: workspace of %zu bytes, %zu needed (anerf_mesh_compact_workspace)", who,
-                 ws_bytes, pl->bytes);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+                  size_t ws_bytes, ScanSpace* pl) {
+    if (!plan(nv, nt, pl))
+        return failf(ANERF_EINVAL, "%s: n_vertices %lld / n_tri %lld must be in [0, 2^31)", who, (long long)nv,
+                     (long long)nt);
+    if ((nv > 0 && !keep) || (nt > 0 && !tri) || !ws)
+        return failf(ANERF_EINVAL, "%s: NULL keep, triangles or workspace", who);
+    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    if (ws_bytes < pl->bytes)
+        return failf(ANERF_EINVAL, "%s: workspace of %zu bytes, %zu needed (anerf_mesh_compact_workspace)", who,
+                     ws_bytes, pl->bytes);
     return ANERF_OK;
 }
-
-int launched(const char* who) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ANERF_OK;
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(e));
-    return anerf_internal_fail(ANERF_EHIP, msg);
-}
-
-int blocks_for(long long n, int threads = NTHR) { return (int)((n + threads - 1) / threads); }
 
 // ------------------------------------------------------------------ vertex adjacency (CSR)
 constexpr int SHORT_ROW = 64;         // the raw entries one thread sorts at most; longer rows go to a workgroup
@@ -417,8 +337,7 @@ struct AdjPlan {
 
 bool adj_plan(int64_t nv, AdjPlan* pl) {
     if (nv < 0 || nv > MAXN) return false;
-    pl->nblocks = (int)((nv + TILE - 1) / TILE);
-    if (pl->nblocks < 1) pl->nblocks = 1;  // (no vertices: offsets[0] and the totals are still written)
+    pl->nblocks = nv > 0 ? tiles_for(nv) : 1;  // (no vertices: offsets[0] and the totals are still written)
     size_t o = 0;
     pl->raw_off = o, o += (size_t)nv + 1;
     pl->cnt = o, o += (size_t)nv;
@@ -586,7 +505,8 @@ __global__ __launch_bounds__(NTHR) void adj_long_rows_kernel(const int* __restri
 }
 
 // Exclusive scan of in[0, n) into out[0, n] (out[n]: the sum, which fits an int: at most 6 T < 2^31), the block-sum
-// pattern of the compaction above: per-tile sums (and maxima) -> one workgroup scans them -> per-tile scan.
+// pattern of anerf_scan.hpp on its tiles and block scan: per-tile sums (and maxima) -> one workgroup scans them ->
+// per-tile scan.  Kept here, not there: one int array, and the row maximum that becomes totals[1] rides along.
 __global__ __launch_bounds__(NTHR) void tile_reduce_kernel(const int* __restrict__ in, int n, int* __restrict__ block_sum,
                                                            int* __restrict__ block_max) {
     __shared__ int lds[NTHR];
@@ -788,23 +708,18 @@ size_t anerf_mesh_components_workspace(int64_t n_vertices, int64_t n_tri) {
 int anerf_mesh_components(const int32_t* triangles, int64_t n_tri, int64_t n_vertices, int32_t* root,
                           int32_t* tri_count, int32_t* vert_count, int64_t* n_components, void* ws, size_t ws_bytes,
                           void* stream) {
-    char msg[256];
-    if (n_tri < 0 || n_vertices < 0 || n_tri > MAXN || n_vertices > MAXN) {
-        snprintf(msg, sizeof msg, "anerf_mesh_components: n_tri %lld / n_vertices %lld must be in [0, 2^31)",
-                 (long long)n_tri, (long long)n_vertices);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (n_tri < 0 || n_vertices < 0 || n_tri > MAXN || n_vertices > MAXN)
+        return failf(ANERF_EINVAL, "anerf_mesh_components: n_tri %lld / n_vertices %lld must be in [0, 2^31)",
+                     (long long)n_tri, (long long)n_vertices);
     if (!n_components) return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_components: NULL n_components");
     if (n_tri > 0 && !triangles) return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_components: NULL triangles");
     if (n_vertices > 0 && (!root || !tri_count || !vert_count || !ws))
         return anerf_internal_fail(ANERF_EINVAL,
                                    "anerf_mesh_components: NULL root, tri_count, vert_count or workspace");
     const size_t need = (size_t)n_vertices * sizeof(int);
-    if (ws_bytes < need) {
-        snprintf(msg, sizeof msg, "anerf_mesh_components: workspace of %zu bytes, %zu needed "
-                 "(anerf_mesh_components_workspace)", ws_bytes, need);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (ws_bytes < need)
+        return failf(ANERF_EINVAL, "anerf_mesh_components: workspace of %zu bytes, %zu needed "
+                     "(anerf_mesh_components_workspace)", ws_bytes, need);
     if ((uintptr_t)ws % 4)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_components: the workspace must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -830,7 +745,7 @@ int anerf_mesh_components(const int32_t* triangles, int64_t n_tri, int64_t n_ver
 }
 
 size_t anerf_mesh_compact_workspace(int64_t n_vertices, int64_t n_tri) {
-    Plan pl;
+    ScanSpace pl;
     if (!plan(n_vertices, n_tri, &pl)) {
         anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_compact_workspace: counts must be in [0, 2^31)");
         return 0;
@@ -840,23 +755,21 @@ size_t anerf_mesh_compact_workspace(int64_t n_vertices, int64_t n_tri) {
 
 int anerf_mesh_compact_count(const uint8_t* keep, int64_t n_vertices, const int32_t* triangles, int64_t n_tri, void* ws,
                              size_t ws_bytes, int64_t* totals_dev, void* stream) {
-    Plan pl;
+    ScanSpace pl;
     const int rc = check_compact("anerf_mesh_compact_count", keep, n_vertices, triangles, n_tri, ws, ws_bytes, &pl);
     if (rc != ANERF_OK) return rc;
     if (!totals_dev) return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_compact_count: NULL totals");
     const Lists l = {keep, triangles, (long long)n_vertices, (long long)n_tri};
-    long long* base = (long long*)ws;
-    int* counts = (int*)((char*)ws + pl.off_counts);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(count_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, l, counts, pl.nblocks);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(NTHR), 0, s, counts, base, pl.nblocks, (long long*)totals_dev);
+    hipLaunchKernelGGL(count_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, l, pl.counts(ws), pl.nblocks);
+    scan_block_sums(pl, ws, totals_dev, s);
     return launched("anerf_mesh_compact_count");
 }
 
 int anerf_mesh_compact_emit(const uint8_t* keep, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
                             const void* ws, size_t ws_bytes, int32_t* vertex_map, int32_t* kept, int64_t max_kept,
                             int32_t* triangles_out, int64_t max_triangles, void* stream) {
-    Plan pl;
+    ScanSpace pl;
     const int rc = check_compact("anerf_mesh_compact_emit", keep, n_vertices, triangles, n_tri, ws, ws_bytes, &pl);
     if (rc != ANERF_OK) return rc;
     if (max_kept < 0 || max_triangles < 0 || max_kept > MAXN || max_triangles > MAXN)
@@ -887,24 +800,19 @@ size_t anerf_mesh_adjacency_workspace(int64_t n_vertices, int64_t n_tri) {
 
 int anerf_mesh_adjacency_count(const int32_t* triangles, int64_t n_tri, int64_t n_vertices, void* ws, size_t ws_bytes,
                                int32_t* offsets, uint8_t* boundary, int64_t* totals_dev, void* stream) {
-    char msg[256];
     AdjPlan pl;
-    if (!adj_plan(n_vertices, &pl) || n_tri < 0 || n_tri > MAXN / 6) {
-        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_count: n_vertices %lld must be in [0, 2^31) and 6 n_tri "
-                 "(n_tri %lld) below 2^31", (long long)n_vertices, (long long)n_tri);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (!adj_plan(n_vertices, &pl) || n_tri < 0 || n_tri > MAXN / 6)
+        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_count: n_vertices %lld must be in [0, 2^31) and 6 n_tri "
+                     "(n_tri %lld) below 2^31", (long long)n_vertices, (long long)n_tri);
     if (!offsets || !totals_dev || !ws || (n_tri > 0 && !triangles) || (n_vertices > 0 && !boundary))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: NULL offsets, totals or workspace, or "
                                                  "NULL triangles or boundary with a non-zero extent");
     if ((uintptr_t)ws % 4)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: the workspace must be 4-byte aligned");
     const size_t need = (pl.raw + (size_t)6 * (size_t)n_tri) * sizeof(int);
-    if (ws_bytes < need) {
-        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_count: workspace of %zu bytes, %zu needed "
-                 "(anerf_mesh_adjacency_workspace)", ws_bytes, need);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (ws_bytes < need)
+        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_count: workspace of %zu bytes, %zu needed "
+                     "(anerf_mesh_adjacency_workspace)", ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int nv = (int)n_vertices;
     const long long nt = (long long)n_tri;
@@ -931,23 +839,18 @@ int anerf_mesh_adjacency_count(const int32_t* triangles, int64_t n_tri, int64_t 
 
 int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, const int32_t* offsets,
                               int32_t* neighbors, int64_t max_neighbors, void* stream) {
-    char msg[256];
     AdjPlan pl;
-    if (!adj_plan(n_vertices, &pl) || max_neighbors < 0 || max_neighbors > MAXN) {
-        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_emit: n_vertices %lld / max_neighbors %lld must be in "
-                 "[0, 2^31)", (long long)n_vertices, (long long)max_neighbors);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (!adj_plan(n_vertices, &pl) || max_neighbors < 0 || max_neighbors > MAXN)
+        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_emit: n_vertices %lld / max_neighbors %lld must be in "
+                     "[0, 2^31)", (long long)n_vertices, (long long)max_neighbors);
     if (!offsets || !ws || (max_neighbors > 0 && !neighbors))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: NULL offsets or workspace, or NULL "
                                                  "neighbors with a non-zero capacity");
     if ((uintptr_t)ws % 4)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: the workspace must be 4-byte aligned");
-    if (ws_bytes < pl.raw * sizeof(int)) {
-        snprintf(msg, sizeof msg, "anerf_mesh_adjacency_emit: workspace of %zu bytes, at least %zu needed "
-                 "(anerf_mesh_adjacency_workspace)", ws_bytes, pl.raw * sizeof(int));
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+    if (ws_bytes < pl.raw * sizeof(int))
+        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_emit: workspace of %zu bytes, at least %zu needed "
+                     "(anerf_mesh_adjacency_workspace)", ws_bytes, pl.raw * sizeof(int));
     const int nv = (int)n_vertices;
     if (nv == 0 || max_neighbors == 0) return ANERF_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -966,14 +869,11 @@ int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, con
 int anerf_mesh_smooth(const float* positions, int64_t n_vertices, const int32_t* offsets, const int32_t* neighbors,
                       int64_t n_neighbors, const uint8_t* pinned, int32_t iterations, float lambda, float mu,
                       int32_t flags, float* out, float* scratch, void* stream) {
-    char msg[256];
     if (n_vertices < 0 || n_vertices > MAXN || n_neighbors < 0 || n_neighbors > MAXN || iterations < 0 ||
-        iterations > 0x3fffffff || (flags & ~ANERF_SMOOTH_TAUBIN)) {
-        snprintf(msg, sizeof msg, "anerf_mesh_smooth: n_vertices %lld / n_neighbors %lld must be in [0, 2^31), "
-                 "iterations %d in [0, 2^30), flags %d a combination of ANERF_SMOOTH_*", (long long)n_vertices,
-                 (long long)n_neighbors, (int)iterations, (int)flags);
-        return anerf_internal_fail(ANERF_EINVAL, msg);
-    }
+        iterations > 0x3fffffff || (flags & ~ANERF_SMOOTH_TAUBIN))
+        return failf(ANERF_EINVAL, "anerf_mesh_smooth: n_vertices %lld / n_neighbors %lld must be in [0, 2^31), "
+                     "iterations %d in [0, 2^30), flags %d a combination of ANERF_SMOOTH_*", (long long)n_vertices,
+                     (long long)n_neighbors, (int)iterations, (int)flags);
     const int steps = iterations * ((flags & ANERF_SMOOTH_TAUBIN) ? 2 : 1);
     if (n_vertices > 0 && (!positions || !out || !offsets || (steps > 1 && !scratch)))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_smooth: NULL positions, out or offsets, or NULL scratch "
@@ -988,11 +888,7 @@ int anerf_mesh_smooth(const float* positions, int64_t n_vertices, const int32_t*
     const int nv = (int)n_vertices;
     if (steps == 0) {
         const hipError_t e = hipMemcpyAsync(out, positions, bytes, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) {
-            snprintf(msg, sizeof msg, "anerf_mesh_smooth: %s", hipGetErrorString(e));
-            return anerf_internal_fail(ANERF_EHIP, msg);
-        }
-        return ANERF_OK;
+        return e == hipSuccess ? ANERF_OK : failf(ANERF_EHIP, "anerf_mesh_smooth: %s", hipGetErrorString(e));
     }
     // step i writes `out` when an even number of steps follows it: the last one always does
     const float* src = positions;

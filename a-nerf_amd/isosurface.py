@@ -84,9 +84,7 @@ def isosurface(volume, threshold, relu=False, flip=False, normals=False):
     flags = _flags(relu, flip)
     with torch.cuda.device(dev):
         stream = _lib.stream_handle(dev)
-        need = lib.anerf_isosurface_workspace(n0, n1, n2)
-        if need == 0:
-            raise _lib.AnerfError(f"anerf_isosurface_workspace: {lib.anerf_last_error().decode(errors='replace')}")
+        need = _lib.workspace("anerf_isosurface_workspace", n0, n1, n2)
         ws = torch.empty(need, device=dev, dtype=torch.uint8)
         totals = torch.empty(2, device=dev, dtype=torch.int64)
         _lib.check(lib.anerf_isosurface_count(_lib.ptr(vol), n0, n1, n2, float(threshold), flags, _lib.ptr(ws), need,
@@ -124,9 +122,7 @@ def isosurface_reference(volume, threshold, relu=False, flip=False, normals=Fals
     """NumPy implementation of the same contract (same table, same fp32 arithmetic, same order): the checker
     of `isosurface`.  Returns (vertices float32 [V, 3], triangles int32 [T, 3]) as arrays, and with
     `normals=True` the vertex normals float32 [V, 3] as the third."""
-    if isinstance(volume, torch.Tensor):
-        volume = volume.detach().cpu().numpy()
-    v = np.ascontiguousarray(volume, dtype=np.float32)
+    v = np.ascontiguousarray(_lib.host_array(volume), dtype=np.float32)
     if v.ndim != 3 or min(v.shape) < 1:
         raise ValueError(f"isosurface_reference takes a non-empty 3-D grid, got shape {v.shape}")
     if relu:
@@ -196,8 +192,7 @@ def isosurface_reference(volume, threshold, relu=False, flip=False, normals=Fals
 
 
 def _host(x, dtype):
-    x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    return np.ascontiguousarray(x, dtype=dtype).reshape(-1, 3)
+    return np.ascontiguousarray(_lib.host_array(x), dtype=dtype).reshape(-1, 3)
 
 
 def write_ply(path, vertices, triangles, normals=None, colors=None):
@@ -221,7 +216,7 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
             raise ValueError(f"write_ply: {len(n)} normals for {len(v)} vertices")
         rec["n"] = n
     if colors is not None:
-        c = colors.detach().cpu().numpy() if isinstance(colors, torch.Tensor) else np.asarray(colors)
+        c = _lib.host_array(colors)
         if c.dtype != np.uint8:
             with np.errstate(invalid="ignore"):
                 c = np.clip(np.rint(np.float32(255) * c.astype(np.float32)), 0, 255)
@@ -343,11 +338,14 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
         from .meshops import smooth_mesh
         v = smooth_mesh(v, t, iterations=smooth, lam=smooth_lambda, mu=smooth_mu, pin="boundary")
     vi = v
-    if coords == "unit":
-        v = v / res - .5
     kp0 = torch.as_tensor(kps).to(v.device, torch.float32).reshape(-1, 3)[0]
-    if coords == "world":
-        v = (-radius + (2.0 * radius / res) * vi[:, [1, 0, 2]]) + kp0
+
+    def world():  # the index-to-world mapping of the docstring, of the (smoothed) index vertices
+        return (-radius + (2.0 * radius / res) * vi[:, [1, 0, 2]]) + kp0
+    if coords == "unit":
+        v = vi / res - .5
+    elif coords == "world":
+        v = world()
     if not (normals or colors):
         return v, t
     attrs = {}
@@ -359,7 +357,7 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
         if len(v) == 0:
             attrs["colors"] = torch.zeros((0, 3), device=v.device, dtype=torch.float32)
         else:
-            vw = v if coords == "world" else (-radius + (2.0 * radius / res) * vi[:, [1, 0, 2]]) + kp0
+            vw = v if coords == "world" else world()
             if one_dir is not None:
                 dirs = one_dir.to(v.device)
             else:

@@ -117,9 +117,7 @@ def _components(t, n_vertices):
 def mesh_components_reference(triangles, n_vertices):
     """NumPy implementation of the same contract, the checker of `mesh_components`: minimum-label propagation over
     the triangles with pointer jumping, until nothing changes.  Returns MeshComponents of arrays."""
-    if isinstance(triangles, torch.Tensor):
-        triangles = triangles.detach().cpu().numpy()
-    tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    tri = np.ascontiguousarray(_lib.host_array(triangles), dtype=np.int64).reshape(-1, 3)
     nv = int(n_vertices)
     if len(tri) and (tri.min() < 0 or tri.max() >= nv):
         raise ValueError(f"mesh_components_reference: vertex ids span [{tri.min()}, {tri.max()}], outside [0, {nv})")
@@ -191,9 +189,7 @@ def _compact(keep, t):
     lib = _lib.load()
     with torch.cuda.device(dev):
         stream = _lib.stream_handle(dev)
-        need = lib.anerf_mesh_compact_workspace(nv, nt)
-        if need == 0:
-            raise _lib.AnerfError(f"anerf_mesh_compact_workspace: {lib.anerf_last_error().decode(errors='replace')}")
+        need = _lib.workspace("anerf_mesh_compact_workspace", nv, nt)
         ws = torch.empty(need, device=dev, dtype=torch.uint8)
         totals = torch.empty(2, device=dev, dtype=torch.int64)
         _lib.check(lib.anerf_mesh_compact_count(_lib.ptr(keep), nv, _lib.ptr(t), nt, _lib.ptr(ws), need,
@@ -241,8 +237,7 @@ def filter_mesh(vertices, triangles, attrs=None, keep_largest=None, min_triangle
 
 def filter_mesh_reference(vertices, triangles, attrs=None, keep_largest=None, min_triangles=0):
     """NumPy implementation of `filter_mesh`'s contract on `mesh_components_reference`: its checker."""
-    def host(x):
-        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    host = _lib.host_array
     v = host(vertices)
     tri = np.ascontiguousarray(host(triangles), dtype=np.int32).reshape(-1, 3)
     if keep_largest is None and int(min_triangles) <= 0:
@@ -268,9 +263,7 @@ def _adjacency(t, n_vertices):
         raise ValueError(f"vertex_adjacency: {nt} triangles list {6 * nt} pairs, which do not fit int32 offsets")
     with torch.cuda.device(dev):
         stream = _lib.stream_handle(dev)
-        need = lib.anerf_mesh_adjacency_workspace(nv, nt)
-        if need == 0:
-            raise _lib.AnerfError(f"anerf_mesh_adjacency_workspace: {lib.anerf_last_error().decode(errors='replace')}")
+        need = _lib.workspace("anerf_mesh_adjacency_workspace", nv, nt)
         ws = torch.empty(need, device=dev, dtype=torch.uint8)
         offsets = torch.empty(nv + 1, device=dev, dtype=torch.int32)
         boundary = torch.empty(nv, device=dev, dtype=torch.uint8)
@@ -307,9 +300,7 @@ def _listed_pairs(tri):
 def vertex_adjacency_reference(triangles, n_vertices):
     """NumPy implementation of the adjacency's contract, the checker of `vertex_adjacency`: the listed pairs as
     sorted keys v * V + u, their distinct values and multiplicities.  Returns VertexAdjacency of arrays."""
-    if isinstance(triangles, torch.Tensor):
-        triangles = triangles.detach().cpu().numpy()
-    tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    tri = np.ascontiguousarray(_lib.host_array(triangles), dtype=np.int64).reshape(-1, 3)
     nv = int(n_vertices)
     if len(tri) and (tri.min() < 0 or tri.max() >= nv):
         raise ValueError(f"vertex_adjacency_reference: vertex ids span [{tri.min()}, {tri.max()}], outside [0, {nv})")
@@ -410,8 +401,7 @@ def _smooth_step_reference(p, offsets, neighbors, w, pinned):
 def smooth_mesh_reference(vertices, triangles, iterations=10, lam=0.5, mu=-0.53, pin="boundary", adjacency=None):
     """NumPy implementation of `smooth_mesh`'s contract on `vertex_adjacency_reference`: its checker.  float32
     throughout; returns an array [V, 3]."""
-    def host(x):
-        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    host = _lib.host_array
     v = host(vertices)
     _smooth_args(v.shape, iterations, lam, mu, "smooth_mesh_reference")
     p = np.array(v, dtype=np.float32)

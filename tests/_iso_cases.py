@@ -76,6 +76,35 @@ def last_rows_field():
     return _ro(1.45 - d)
 
 
+# Grids of exactly 1024, 1025 (one workgroup's tile of points, + 1) and 262143, 262144, 262145 points (the 256 tiles
+# of one round of the one-workgroup scan, -1, +0, +1)
+TILE_EDGE_SHAPES = ((8, 8, 16), (5, 5, 41), (27, 133, 73), (64, 64, 64), (65, 37, 109))
+
+
+@functools.lru_cache(maxsize=None)
+def tile_edge_field(shape, corner=False):
+    """A sphere of radius 0.3 min(shape) about the grid's centre and a ball of radius 1.6 three points in from the far
+    corner, inside = high, threshold 0.  That ball ends two rows short of the last row of axis 0, so the last
+    workgroups' tiles stay empty; `corner` puts a ball of radius 1.45 around the far corner point instead (a surface
+    cut open by the grid's end): the edge two points before the corner along the last axis crosses, so the base of
+    the last tile that owns an edge matters."""
+    x, y, z = _coords(shape)
+    c = [(n - 1) / 2 for n in shape]
+    q, r = ([n - 1 for n in shape], 1.45) if corner else ([n - 4 for n in shape], 1.6)
+    sphere = 0.3 * min(shape) - np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2)
+    ball = r - np.sqrt((x - q[0]) ** 2 + (y - q[1]) ** 2 + (z - q[2]) ** 2)
+    return _ro(np.maximum(sphere, ball))
+
+
+@functools.lru_cache(maxsize=None)
+def tile_edge_reference(shape, corner=False):
+    """isosurface_reference (vertices, triangles, normals) of tile_edge_field(shape, corner), read-only."""
+    out = iso.isosurface_reference(tile_edge_field(shape, corner), 0.0, normals=True)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def relu_field():
     """Values on both sides of 0 and a positive threshold (0.25): the clamp moves the vertices of every edge whose

@@ -62,13 +62,21 @@ def relabelled(name, kind):
 
 # ------------------------------------------------------------------ lists whose answer is known by construction
 STRIP_T = 300000  # (300,002 vertices: more than one 256 x 1024 tile of the block-sum scan)
+# One workgroup's tile of 1024 items, and the 256 tiles one round of the one-workgroup scan takes, each -1, +0, +1
+TILE_EDGES = (1023, 1024, 1025, 262143, 262144, 262145)
+
+
+@functools.lru_cache(maxsize=None)
+def strip_triangles(nv):
+    """The nv - 2 triangles (i, i + 1, i + 2) of one strip over nv vertices (read-only)."""
+    return _ro((np.arange(nv - 2, dtype=np.int64)[:, None] + np.arange(3)).astype(np.int32))[0]
 
 
 @functools.lru_cache(maxsize=None)
 def strip(shuffled=False):
     """One strip (i, i + 1, i + 2): (triangles, V, components).  One component with root 0, ids shuffled or not."""
     nv = STRIP_T + 2
-    tri = (np.arange(STRIP_T, dtype=np.int64)[:, None] + np.arange(3)).astype(np.int32)
+    tri = strip_triangles(nv)
     if shuffled:
         tri = relabel(tri, np.random.default_rng(99).permutation(nv))
     comp = meshops.MeshComponents(np.zeros(nv, np.int32), np.zeros(1, np.int32), np.array([STRIP_T], np.int64),

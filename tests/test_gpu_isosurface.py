@@ -73,6 +73,29 @@ def test_matches_the_reference(name):
     assert np.isfinite(v).all()
 
 
+@pytest.mark.parametrize("corner", [False, True], ids=["ball_3_in", "ball_in_the_corner"])
+@pytest.mark.parametrize("shape", C.TILE_EDGE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_matches_the_reference_at_the_scan_tile_edges(shape, corner):
+    """1024 and 1025 points, and 262143, 262144, 262145: one tile + 1, and one round of the block-sum scan -1, +0, +1
+    (at 257 workgroups its carry starts: the totals come through it).  Positions and normals bit for bit.  With the
+    ball in the corner the point (n0 - 1, n1 - 1, n2 - 3) owns the last vertex: the base of the last tile with edges."""
+    points = int(np.prod(shape))
+    assert points in (1024, 1025, 262143, 262144, 262145)
+    rv, rt, rn = C.tile_edge_reference(shape, corner)
+    assert len(rt) > 0
+    if corner:
+        owner = np.floor(rv).astype(np.int64) @ np.array([shape[1] * shape[2], shape[2], 1])
+        assert int(owner.max()) == points - 3
+    v, t, n = iso.isosurface(C.tile_edge_field(shape, corner), 0.0, normals=True)
+    np.testing.assert_array_equal(t.cpu().numpy(), rt)
+    for name, got, ref in (("positions", v, rv), ("normals", n, rn)):
+        got = got.cpu().numpy()
+        assert got.dtype == np.float32 and got.shape == ref.shape, (name, got.shape, ref.shape)
+        diff = int((got.view(np.int32) != ref.view(np.int32)).sum())
+        print(f"{shape} {name}: {diff} differing words of {ref.size}")
+        assert diff == 0, name
+
+
 def test_flip_reverses_the_winding():
     v, t = iso.isosurface(C.sphere_field(), 0.0, flip=True)
     _assert_same((v, t), C.reference("sphere_field", flip=True), "flip")

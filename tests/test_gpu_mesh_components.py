@@ -159,6 +159,19 @@ def test_compact_alternating_runs_of_the_strip():
     np.testing.assert_array_equal(kept.cpu().numpy()[first], old)
 
 
+@pytest.mark.parametrize("nv", M.TILE_EDGES)
+def test_compact_at_the_scan_tile_edges(nv):
+    """One tile of 1024 items and the 256 tiles of one round of the block-sum scan, each -1, +0, +1 vertices: runs of
+    5 kept / 5 dropped, so every tile counts vertices and triangles; the last vertex is kept at each of these sizes,
+    and in the + 1 lists it is the last tile's only item (its new id is that tile's base)."""
+    tri = M.strip_triangles(nv)
+    keep = ((np.arange(nv) // 5) % 2 == 0).astype(np.uint8)
+    kept, out = _assert_compact(keep, tri, f"strip of {nv} vertices")
+    runs, tail = divmod(nv, 10)  # by construction: 5 vertices and 3 triangles per whole kept run
+    assert len(kept) == 5 * runs + min(tail, 5) and len(out) == 3 * runs + max(min(tail, 5) - 2, 0)
+    assert int(kept[-1]) == nv - 1
+
+
 def test_deterministic_and_stream_independent():
     tri, nv, ref = _list("random33/permuted")
     t = torch.from_numpy(np.array(tri)).cuda()

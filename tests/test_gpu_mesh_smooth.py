@@ -60,6 +60,16 @@ def test_adjacency_matches(case):
     _assert_adjacency(meshops.vertex_adjacency(_dev(tri), nv), S.adjacency(case), case)
 
 
+@pytest.mark.parametrize("nv", M.TILE_EDGES)
+def test_adjacency_at_the_scan_tile_edges(nv):
+    """Strips of one tile of 1024 vertices and of the 256 tiles of one round of the base scan, each -1, +0, +1: both
+    scans of the count entry (raw offsets, then offsets) and the last tile's base in the emit pass."""
+    tri = M.strip_triangles(nv)
+    adj = meshops.vertex_adjacency(_dev(tri), nv)
+    _assert_adjacency(adj, meshops.vertex_adjacency_reference(tri, nv), f"strip of {nv} vertices")
+    assert int(adj.offsets[-1]) == 4 * nv - 6  # by construction: degree 4 inside, 2 and 3 at either end
+
+
 def test_wheel_by_construction():
     tri, nv = S.wheel(5000)
     adj = meshops.vertex_adjacency(_dev(tri), nv)

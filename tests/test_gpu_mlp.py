@@ -662,9 +662,9 @@ def test_backward_hidden_deferred_reduce_is_identical():
                                                      P(db0), P(ws), ws.numel(), mlp._stream(dev)), "direct")
         mlp._lib.check(lib.anerf_mlp_backward_hidden(m, 256, P(dy), 256, P(x), 256, P(wt), 3, P(dx), 256, None, 256,
                                                      None, P(ws), ws.numel(), mlp._stream(dev)), "deferred")
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
         dw1, db1 = torch.full((256, 256), 3.0, device=DEV), torch.full((256,), 3.0, device=DEV)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))  # (after the fills above: they run on the current stream)
         with torch.cuda.stream(side):
             mlp._lib.check(lib.anerf_mlp_backward_hidden_reduce(m, 256, P(ws), ws.numel(), P(dw1), 256, P(db1),
                                                                 mlp._stream(dev)), "reduce")
