@@ -9,8 +9,9 @@ from .config import RenderConfig, flops_per_sample, samples_per_ray
 from .raycaster import RayCaster, create_raycaster, load_checkpoint
 from .render import batchify_rays, render, render_path, render_frames
 from .isosurface import isosurface, isosurface_reference, mesh_from_grid, read_ply, render_mesh, write_ply
-from .meshops import (filter_mesh, mesh_components, mesh_components_reference, smooth_mesh, smooth_mesh_reference,
-                      vertex_adjacency, vertex_adjacency_reference)
+from .meshops import (filter_mesh, mesh_components, mesh_components_reference, mesh_turntable, rasterize_mesh,
+                      rasterize_mesh_reference, smooth_mesh, smooth_mesh_reference, turntable_transforms,
+                      vertex_adjacency, vertex_adjacency_reference, vertex_normals, vertex_normals_reference)
 from . import dataset, rays, synthetic, train
 from .dataset import RayImageDataset, RayImageSampler
 
@@ -18,4 +19,6 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
            "isosurface", "isosurface_reference", "mesh_from_grid", "read_ply", "render_mesh", "write_ply",
            "mesh_components", "mesh_components_reference", "filter_mesh", "vertex_adjacency",
-           "vertex_adjacency_reference", "smooth_mesh", "smooth_mesh_reference"]
+           "vertex_adjacency_reference", "smooth_mesh", "smooth_mesh_reference", "vertex_normals",
+           "vertex_normals_reference", "rasterize_mesh", "rasterize_mesh_reference", "mesh_turntable",
+           "turntable_transforms"]

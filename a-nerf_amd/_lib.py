@@ -37,7 +37,8 @@ ANERF_ENC_KP_RELPOS, ANERF_ENC_VIEW_ANGLE = 16, 32  # --kp_dist_type relpos, --v
 ANERF_ENC_KP_QUERYPTS = 64  # --kp_dist_type querypts (staged, ABI 15)
 ANERF_ENC_VIEW_WINDOWS = 128  # training layout: the view part as the NJ view windows (ABI 16)
 ANERF_SMOOTH_TAUBIN = 1  # anerf_mesh_smooth's flags: a step with mu after every step with lambda
-ABI_VERSION = 23  # include/anerf.h ANERF_ABI_VERSION: the structs below
+ANERF_RASTER_SMALL_PIXELS = 256  # include/anerf.h: the clipped bounding box up to which a triangle's own thread draws it
+ABI_VERSION = 24  # include/anerf.h ANERF_ABI_VERSION: the structs below
 
 
 class ModelDesc(ctypes.Structure):
@@ -174,6 +175,15 @@ SIGNATURES = {
     "anerf_mesh_smooth": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
                                          ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "anerf_mesh_vertex_normals_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "anerf_mesh_vertex_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "anerf_mesh_raster_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "anerf_mesh_raster": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
     "anerf_radiance_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32,

@@ -5,10 +5,10 @@ include/anerf.h is stored next to the library (`libanerf_hip.so.stamp`).  A ship
 stamp does not match the sources is rebuilt, never reused because of its mtime.
 
 The translation units compile in parallel into objects cached under `.objs/` by the hash of
-their own dependencies (anerf_gemm.hip reads only include/anerf.h; anerf_iso.hip and anerf_mesh.hip that and
-csrc/anerf_scan.hpp, which no other unit reads, anerf_iso.hip also its case table), then link into the library: an
-edit of the training GEMMs, of the iso-surface or of the mesh kernels recompiles one unit, an edit of their shared
-scan header those two, never the render kernels' instances.
+their own dependencies (anerf_gemm.hip reads only include/anerf.h; anerf_iso.hip, anerf_mesh.hip and
+anerf_raster.hip that and csrc/anerf_scan.hpp, which no other unit reads, anerf_iso.hip also its case table), then
+link into the library: an edit of the training GEMMs, of the iso-surface, of the mesh or of the raster kernels
+recompiles one unit, an edit of their shared scan header those three, never the render kernels' instances.
 """
 import hashlib
 import os
@@ -20,8 +20,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "anerf.h")
 SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_gemm.hip"),
-       os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip")]
-SCAN_HEADER = os.path.join(CSRC, "anerf_scan.hpp")  # anerf_iso.hip's and anerf_mesh.hip's alone
+       os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip"),
+       os.path.join(CSRC, "anerf_raster.hip")]
+SCAN_HEADER = os.path.join(CSRC, "anerf_scan.hpp")  # anerf_iso.hip's, anerf_mesh.hip's and anerf_raster.hip's alone
 OUT = os.path.join(HERE, "libanerf_hip.so")
 STAMP = OUT + ".stamp"
 OBJS = os.path.join(HERE, ".objs")
@@ -50,12 +51,13 @@ def source_hash():
 
 
 def unit_deps(src):
-    """The files a translation unit reads: anerf_gemm.hip only the C header; anerf_mesh.hip and anerf_iso.hip the
-    scan header and the C header, anerf_iso.hip its case table as well; anerf_render.hip every other csrc header."""
+    """The files a translation unit reads: anerf_gemm.hip only the C header; anerf_mesh.hip, anerf_raster.hip and
+    anerf_iso.hip the scan header and the C header, anerf_iso.hip its case table as well; anerf_render.hip every other
+    csrc header."""
     name = os.path.basename(src)
     if name == "anerf_gemm.hip":
         return [src, HEADER]
-    if name == "anerf_mesh.hip":
+    if name in ("anerf_mesh.hip", "anerf_raster.hip"):
         return [src, SCAN_HEADER, HEADER]
     if name == "anerf_iso.hip":
         return [src, os.path.join(CSRC, "anerf_iso_table.inc"), SCAN_HEADER, HEADER]

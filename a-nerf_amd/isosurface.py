@@ -310,7 +310,11 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     pin="boundary"; smooth_mu=None: plain Laplacian) right after the component filter, in index coordinates, before
     the `unit` / `world` mapping: the colours are queried at the smoothed world vertices.  attrs["normals"] stay the
     gradient normals of the UNSMOOTHED crossing (face-based normals of the smoothed surface are not computed), and
-    they still give the view directions of view="normal".  With smooth=0 that code is not entered."""
+    they still give the view directions of view="normal".  With smooth=0 that code is not entered.
+    `normals="faces"`: attrs["normals"] are instead the face-accumulated normals (meshops.vertex_normals, the
+    colouring of the reference's viewer) of the FINAL vertices -- after the filter, the smoothing and the `coords`
+    mapping, for the winding returned -- and with view="normal" these give the view directions of the colour query;
+    the grid's gradient is not evaluated.  normals=True / False behave as before."""
     if coords not in ("unit", "index", "world"):
         raise ValueError(f"coords must be 'unit', 'index' or 'world', got {coords!r}")
     one_dir = None
@@ -321,8 +325,11 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
             one_dir = torch.as_tensor(view, dtype=torch.float32).reshape(-1)
             if one_dir.numel() != 3:
                 raise ValueError(f"view must be 'normal' or one direction (x, y, z), got {view!r}")
+    faces = isinstance(normals, str)
+    if faces and normals != "faces":
+        raise ValueError(f"normals must be True, False or 'faces', got {normals!r}")
     wflip = bool(flip) != (coords == "world")  # the winding's flag in index coordinates
-    need_n = bool(normals) or (bool(colors) and one_dir is None)
+    need_n = not faces and (bool(normals) or (bool(colors) and one_dir is None))
     if need_n:
         v, t, n = isosurface(grid, threshold, relu=True, flip=wflip, normals=True)
     else:
@@ -349,7 +356,14 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     if not (normals or colors):
         return v, t
     attrs = {}
-    if normals:
+    if faces:
+        from .meshops import vertex_normals
+        nf = vertex_normals(v, t)
+        attrs["normals"] = nf
+        # in place of the gradient normal of the index frame: the winding follows `wflip` there, and the axis swap
+        # (a reflection) turns a face normal round, so nf read in index columns is n, negated under "world"
+        n = nf if coords != "world" else (0.0 - nf)[:, [1, 0, 2]]
+    elif normals:
         # (the axis swap is a reflection: a vector follows it as it is, while the winding's flag was reversed for
         # it -- so the extracted normals are negated back; 0 - n keeps a zero normal +0)
         attrs["normals"] = (0.0 - n[:, [1, 0, 2]]) if coords == "world" else n
@@ -377,7 +391,8 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, re
     """Drop-in for run_render.render_mesh (run_render.py:970-986): per pose, the density grid and its iso-surface
     on the device, written to basedir/meshes/{i:03d}.ply in the reference's vertices / res - .5 coordinates.
     Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it).
-    `normals` / `colors` / `view`: as RayCaster.extract_mesh; the attributes go into the PLYs (nx / ny / nz,
+    `normals` (True, or "faces" for the face-accumulated normals of the final vertices) / `colors` / `view`: as
+    RayCaster.extract_mesh; the attributes go into the PLYs (nx / ny / nz,
     red / green / blue) and the list holds (vertices, triangles, attrs).  `keep_largest` / `min_triangles`: the
     component filter of RayCaster.extract_mesh (keep_largest=1: the body without floaters).  `smooth` /
     `smooth_lambda` / `smooth_mu`: its Taubin smoothing, after the filter; the PLYs hold the smoothed vertices, and

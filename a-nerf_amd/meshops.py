@@ -33,8 +33,17 @@ host (trimesh.smoothing.filter_taubin).  `vertex_adjacency` builds the vertex co
     reads only the previous step's positions (Jacobi).  NaN and inf propagate as the arithmetic gives them;
   * one iteration is a step with lam, then a step with mu when mu is given (Taubin's lambda | mu, which does not
     shrink the body as the plain Laplacian does).
+
+Looking at the result is the last step (the reference's render_mesh.py: 91 orthographic views through OpenGL, coloured
+by normals).  `vertex_normals` (anerf_mesh_vertex_normals), `rasterize_mesh` (anerf_mesh_raster) and `mesh_turntable`
+do it on the device, csrc/anerf_raster.hip; their contract, shared with `vertex_normals_reference` /
+`rasterize_mesh_reference` (NumPy checkers, reached only by those names), is written out in include/anerf.h and
+DESIGN.md: quantised face normals summed as 64-bit integers; coverage on vertices snapped to 1 / 256 pixel with
+integer edge functions and a tie rule; a depth test that is one 64-bit atomic min per fragment.  Orthographic / affine
+cameras only: no perspective, no near-plane clipping, no multisampling, and no image files are written.
 """
 import collections
+import ctypes
 
 import numpy as np
 import torch
@@ -43,6 +52,12 @@ from . import _lib
 
 MeshComponents = collections.namedtuple("MeshComponents", ["labels", "roots", "triangle_counts", "vertex_counts"])
 VertexAdjacency = collections.namedtuple("VertexAdjacency", ["offsets", "neighbors", "boundary"])
+MeshRaster = collections.namedtuple("MeshRaster", ["face_ids", "depth", "bary", "image"])
+# the clipped bounding box (in pixel centres) up to which the thread that set a triangle up also draws it
+# (include/anerf.h; larger boxes are drained by workgroups -- the outputs are the same bits either way)
+RASTER_SMALL_PIXELS = _lib.ANERF_RASTER_SMALL_PIXELS
+RASTER_MAX_DIM = 16384
+RASTER_MAX_CHANNELS = 8
 
 
 def _check_ids(triangles, n_vertices, who):
@@ -420,3 +435,377 @@ def smooth_mesh_reference(vertices, triangles, iterations=10, lam=0.5, mu=-0.53,
         if mu is not None:
             p = _smooth_step_reference(p, offsets, neighbors, mu, pinned)
     return p
+
+
+# ------------------------------------------------------------------ face-accumulated vertex normals
+_F = np.float32
+_QUANT = np.float32(2.0 ** 30)
+_NORMAL_EPS = np.float32(1e-8)
+
+
+def _check_vertices(shape, who):
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{who}: vertices must be [V, 3], got shape {tuple(shape)}")
+
+
+@torch.no_grad()
+def vertex_normals(vertices, triangles):
+    """Vertex normals float32 [V, 3] (device) of a mesh (vertices float [V, 3], triangles int [T, 3]) from its faces:
+    every triangle adds its unit normal, with equal weight, to its three vertices, and the sums are normalised -- the
+    colouring of the reference's viewer (render_mesh.py compute_normal), for the winding as given.  The arithmetic is
+    include/anerf.h's contract (fp32, separately rounded; lengths below 1e-8 raised to it, the viewer's normalize_v3;
+    the face normals quantised to 2^-30 and summed as 64-bit integers, so the result is the same on every run), bit
+    for bit that of `vertex_normals_reference`.  A vertex that no triangle uses gets (0, 0, 0).
+    Not mirrored: the viewer's own `norm[faces[:, k]] += n` loses duplicate indices (NumPy's buffered fancy-index add:
+    only one face per column reaches a vertex); its intent, equal-weight accumulation over ALL incident faces, is
+    what is implemented.  An id outside [0, V) raises ValueError before anything is launched.  Three launches on the
+    current stream, no host read."""
+    v = torch.as_tensor(vertices)
+    _check_vertices(tuple(v.shape), "vertex_normals")
+    nv = int(v.shape[0])
+    t = _device_triangles(triangles, nv, "vertex_normals")
+    return _vertex_normals(v.to(t.device, torch.float32).contiguous(), t)
+
+
+def _vertex_normals(p, t):
+    dev = t.device
+    lib = _lib.load()
+    nv, nt = int(p.shape[0]), int(t.shape[0])
+    with torch.cuda.device(dev):
+        need = _lib.workspace("anerf_mesh_vertex_normals_workspace", nv, nt)
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        out = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+        _lib.check(lib.anerf_mesh_vertex_normals(_lib.ptr(p), nv, _lib.ptr(t), nt, _lib.ptr(out), _lib.ptr(ws), need,
+                                                 _lib.stream_handle(dev)), "anerf_mesh_vertex_normals")
+    return out
+
+
+def _normalize_reference(n):
+    """n / max(|n|, 1e-8) on float32 [N, 3], |n| = sqrt((x x + y y) + z z)."""
+    with np.errstate(all="ignore"):
+        ln = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+        ln = np.where(ln < _NORMAL_EPS, _NORMAL_EPS, ln)  # (a NaN length stays)
+        return (n / ln[:, None]).astype(_F)
+
+
+def _host_triangles(triangles, nv, who):
+    tri = np.ascontiguousarray(_lib.host_array(triangles), dtype=np.int64).reshape(-1, 3)
+    if len(tri) and (tri.min() < 0 or tri.max() >= nv):
+        raise ValueError(f"{who}: vertex ids span [{tri.min()}, {tri.max()}], outside [0, {nv})")
+    return tri
+
+
+def vertex_normals_reference(vertices, triangles):
+    """NumPy implementation of `vertex_normals`' contract: its checker.  Returns float32 [V, 3]."""
+    p = np.ascontiguousarray(_lib.host_array(vertices), dtype=_F)
+    _check_vertices(p.shape, "vertex_normals_reference")
+    nv = len(p)
+    tri = _host_triangles(triangles, nv, "vertex_normals_reference")
+    acc = np.zeros((nv, 3), np.int64)
+    if len(tri):
+        with np.errstate(all="ignore"):
+            a = p[tri[:, 0]]
+            e1, e2 = p[tri[:, 1]] - a, p[tri[:, 2]] - a
+            n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                          e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], -1).astype(_F)
+            n = _normalize_reference(n)
+            q = np.where(np.isfinite(n), np.rint(np.where(np.isfinite(n), n, _F(0)) * _QUANT), _F(0)).astype(np.int64)
+        for k in range(3):
+            np.add.at(acc, tri[:, k], q)
+    s = acc.astype(_F) * _F(2.0 ** -30)
+    return _normalize_reference(s)
+
+
+# ------------------------------------------------------------------ the rasteriser
+def _raster_args(vertices_shape, transform, width, height, attrs_shape, background, who):
+    """The argument errors of rasterize_mesh and its checker: (transform float32 [3, 4], C, background float32 [C])."""
+    _check_vertices(vertices_shape, who)
+    A = np.ascontiguousarray(_lib.host_array(transform), dtype=_F)
+    if A.shape != (3, 4):
+        raise ValueError(f"{who}: transform must be [3, 4], got shape {A.shape}")
+    for name, x in (("width", width), ("height", height)):
+        if int(x) != x or not 1 <= int(x) <= RASTER_MAX_DIM:
+            raise ValueError(f"{who}: {name} must be an integer in [1, {RASTER_MAX_DIM}], got {x}")
+    if attrs_shape is None:
+        return A, 0, np.zeros(0, _F)
+    if len(attrs_shape) != 2 or attrs_shape[0] != vertices_shape[0]:
+        raise ValueError(f"{who}: attrs of shape {tuple(attrs_shape)} for {vertices_shape[0]} vertices ([V, C] wanted)")
+    nch = int(attrs_shape[1])
+    if not 1 <= nch <= RASTER_MAX_CHANNELS:
+        raise ValueError(f"{who}: attrs must have 1 to {RASTER_MAX_CHANNELS} channels, got {nch}")
+    bg = np.asarray(background, dtype=_F).reshape(-1)
+    if bg.size == 1:
+        bg = np.repeat(bg, nch)
+    if bg.size != nch:
+        raise ValueError(f"{who}: background must be one value or {nch}, got {bg.size}")
+    return A, nch, np.ascontiguousarray(bg)
+
+
+def _raster_launch(p, t, A, width, height, a, nch, bg, ws):
+    """One anerf_mesh_raster call on checked device tensors (ws: its workspace, reusable between frames)."""
+    dev = t.device
+    lib = _lib.load()
+    face_ids = torch.empty((height, width), device=dev, dtype=torch.int32)
+    depth = torch.empty((height, width), device=dev, dtype=torch.float32)
+    bary = torch.empty((height, width, 3), device=dev, dtype=torch.float32)
+    image = torch.empty((height, width, nch), device=dev, dtype=torch.float32) if nch else None
+    _lib.check(lib.anerf_mesh_raster(_lib.ptr(p), int(p.shape[0]), _lib.ptr(t), int(t.shape[0]),
+                                     A.ctypes.data_as(ctypes.c_void_p), width, height, _lib.ptr(a), nch,
+                                     bg.ctypes.data_as(ctypes.c_void_p) if nch else None, _lib.ptr(face_ids),
+                                     _lib.ptr(depth), _lib.ptr(bary), _lib.ptr(image), _lib.ptr(ws), int(ws.shape[0]),
+                                     _lib.stream_handle(dev)), "anerf_mesh_raster")
+    return MeshRaster(face_ids, depth, bary, image)
+
+
+def _raster_inputs(vertices, triangles, attrs, who):
+    v = torch.as_tensor(vertices)
+    t = _device_triangles(triangles, int(v.shape[0]), who)
+    dev = t.device
+    p = v.to(dev, torch.float32).contiguous()
+    a = None if attrs is None else torch.as_tensor(attrs).to(dev, torch.float32).contiguous()
+    return p, t, a
+
+
+@torch.no_grad()
+def rasterize_mesh(vertices, triangles, transform, width, height, attrs=None, background=1.0):
+    """One orthographic (affine) view of a mesh (vertices float [V, 3], triangles int [T, 3]) on the device.
+    `transform` float [3, 4] (host) maps a vertex to (pixel x, pixel y downward, depth): pixel (row j, column i) has
+    its centre at (i + 0.5, j + 0.5), smaller depths are nearer, and only depths in [0, 1] are drawn.  Returns
+    MeshRaster of device tensors:
+      face_ids int32 [H, W]    the nearest triangle covering the pixel's centre (equal depths: the smaller id), or -1;
+      depth float32 [H, W]     its depth there, +inf where empty;
+      bary float32 [H, W, 3]   its barycentric weights there, 0 where empty;
+      image float32 [H, W, C]  `attrs` float [V, C] (1 <= C <= 8) interpolated with them, `background` (one value or
+                               C) where empty; None without `attrs`.
+    Both windings are drawn (no back-face culling, as in the reference's viewer); a triangle with a vertex that maps
+    to a non-finite value or beyond 2^20 pixels is dropped whole.  The contract (include/anerf.h) is
+    integers wherever a decision is taken, so the result does not depend on the schedule and is bit for bit that of
+    `rasterize_mesh_reference`.  Triangles whose clipped bounding box holds more than RASTER_SMALL_PIXELS pixel
+    centres are drawn by whole workgroups, smaller ones by one thread each: the same bits either way.
+    ValueError before anything is launched: ids outside [0, V), width or height outside [1, 16384], attrs rows != V.
+    Four launches on the current stream, no host read.  Out of scope: perspective cameras and near-plane clipping,
+    multisampling, writing image files."""
+    shape = tuple(vertices.shape) if hasattr(vertices, "shape") else np.shape(vertices)
+    ashape = None if attrs is None else (tuple(attrs.shape) if hasattr(attrs, "shape") else np.shape(attrs))
+    A, nch, bg = _raster_args(shape, transform, width, height, ashape, background, "rasterize_mesh")
+    p, t, a = _raster_inputs(vertices, triangles, attrs, "rasterize_mesh")
+    width, height = int(width), int(height)
+    with torch.cuda.device(t.device):
+        need = _lib.workspace("anerf_mesh_raster_workspace", int(p.shape[0]), int(t.shape[0]), width, height)
+        ws = torch.empty(need, device=t.device, dtype=torch.uint8)
+        return _raster_launch(p, t, A, width, height, a, nch, bg, ws)
+
+
+_RASTER_CHUNK = 1 << 21  # candidate fragments per pass of the checker
+_EMPTY_KEY = np.uint64(0xffffffffffffffff)
+
+
+def _fragments_reference(X, Y, z, a2, flip, tid, i, j):
+    """The contract's fragment of triangles `tid` at pixels (i, j) (arrays of one length): (ok, b0, b1, b2, z)."""
+    px, py = 256 * i + 128, 256 * j + 128
+    inside = np.ones(len(tid), bool)
+    E = {}
+    for a, b in ((1, 2), (2, 0), (0, 1)):
+        dx, dy = X[tid, b] - X[tid, a], Y[tid, b] - Y[tid, a]
+        e = dx * (py - Y[tid, a]) - dy * (px - X[tid, a])
+        sgn = np.where(flip[tid], -1, 1)
+        e, dx, dy = e * sgn, dx * sgn, dy * sgn
+        inside &= (e > 0) | ((e == 0) & ((dy > 0) | ((dy == 0) & (dx < 0))))
+        E[(a, b)] = e
+    with np.errstate(all="ignore"):
+        area = a2[tid].astype(_F)
+        b1 = E[(2, 0)].astype(_F) / area
+        b2 = E[(0, 1)].astype(_F) / area
+        b0 = (_F(1) - b1) - b2
+        zz = (b0 * z[tid, 0] + b1 * z[tid, 1]) + b2 * z[tid, 2]
+        ok = inside & (zz >= 0) & (zz <= 1)
+    zz = np.where(zz == 0, _F(0), zz).astype(_F)
+    return ok, b0, b1, b2, zz
+
+
+def rasterize_mesh_reference(vertices, triangles, transform, width, height, attrs=None, background=1.0):
+    """NumPy implementation of `rasterize_mesh`'s contract: its checker.  Returns MeshRaster of arrays."""
+    p = np.ascontiguousarray(_lib.host_array(vertices), dtype=_F)
+    a = None if attrs is None else np.ascontiguousarray(_lib.host_array(attrs), dtype=_F)
+    A, nch, bg = _raster_args(p.shape, transform, width, height, None if a is None else a.shape, background,
+                              "rasterize_mesh_reference")
+    W, H = int(width), int(height)
+    tri = _host_triangles(triangles, len(p), "rasterize_mesh_reference")
+    keys = np.full(H * W, _EMPTY_KEY, np.uint64)
+    nt = len(tri)
+    if nt:
+        with np.errstate(all="ignore"):
+            s = np.stack([((A[r, 0] * p[:, 0] + A[r, 1] * p[:, 1]) + A[r, 2] * p[:, 2]) + A[r, 3]
+                          for r in range(3)], -1)
+            s = s.astype(_F)[tri]  # [T, 3 vertices, 3]
+            good = np.isfinite(s).all(axis=(1, 2)) & (np.abs(s[..., :2]) <= _F(2.0 ** 20)).all(axis=(1, 2))
+            s = np.where(good[:, None, None], s, _F(0))
+            X = np.rint(s[..., 0] * _F(256)).astype(np.int64)
+            Y = np.rint(s[..., 1] * _F(256)).astype(np.int64)
+        z = np.ascontiguousarray(s[..., 2])
+        a2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
+        flip = a2 < 0
+        a2 = np.abs(a2)
+        i0 = np.maximum((X.min(1) - 128 + 255) >> 8, 0)
+        i1 = np.minimum((X.max(1) - 128) >> 8, W - 1)
+        j0 = np.maximum((Y.min(1) - 128 + 255) >> 8, 0)
+        j1 = np.minimum((Y.max(1) - 128) >> 8, H - 1)
+        live = np.nonzero(good & (a2 != 0) & (i0 <= i1) & (j0 <= j1))[0]
+        bw = (i1 - i0 + 1)[live]
+        box = bw * (j1 - j0 + 1)[live]
+        # candidates (triangle, pixel of its box), a bounded number at a time (a larger box: a pass of its own)
+        start = 0
+        while start < len(live):
+            end = start + max(1, int(np.searchsorted(np.cumsum(box[start:]), _RASTER_CHUNK, side="right")))
+            sel, n = live[start:end], box[start:end]
+            tid = np.repeat(sel, n)
+            k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            w = np.repeat(bw[start:end], n)
+            i, j = i0[tid] + k % w, j0[tid] + k // w
+            ok, _, _, _, zz = _fragments_reference(X, Y, z, a2, flip, tid, i, j)
+            key = (zz[ok].view(np.uint32).astype(np.uint64) << np.uint64(32)) | tid[ok].astype(np.uint64)
+            np.minimum.at(keys, (j[ok] * W + i[ok]), key)
+            start = end
+    hit = np.nonzero(keys != _EMPTY_KEY)[0]
+    face_ids = np.full(H * W, -1, np.int32)
+    depth = np.full(H * W, np.inf, _F)
+    bary = np.zeros((H * W, 3), _F)
+    image = None if a is None else np.tile(bg, (H * W, 1)).astype(_F)
+    if len(hit):
+        tid = (keys[hit] & np.uint64(0xffffffff)).astype(np.int64)
+        ok, b0, b1, b2, zz = _fragments_reference(X, Y, z, a2, flip, tid, hit % W, hit // W)
+        assert ok.all()
+        face_ids[hit] = tid
+        depth[hit] = zz
+        bary[hit] = np.stack([b0, b1, b2], -1)
+        if a is not None:
+            with np.errstate(all="ignore"):
+                a0, a1, a2_ = a[tri[tid, 0]], a[tri[tid, 1]], a[tri[tid, 2]]
+                image[hit] = (b0[:, None] * a0 + b1[:, None] * a1) + b2[:, None] * a2_
+    return MeshRaster(face_ids.reshape(H, W), depth.reshape(H, W), bary.reshape(H, W, 3),
+                      None if image is None else image.reshape(H, W, nch))
+
+
+# ------------------------------------------------------------------ turntable
+def _bounding_box(vertices):
+    """(min, max) float64 [3] over the finite vertices (one read); a mesh without any: the origin."""
+    if isinstance(vertices, torch.Tensor):
+        v = vertices.reshape(-1, 3)
+        v = v[torch.isfinite(v).all(-1)]
+        if v.shape[0] == 0:
+            return np.zeros(3), np.zeros(3)
+        box = torch.stack([v.amin(0), v.amax(0)]).double().cpu().numpy()  # (the one read)
+        return box[0], box[1]
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    v = v[np.isfinite(v).all(-1)]
+    if len(v) == 0:
+        return np.zeros(3), np.zeros(3)
+    return v.min(0), v.max(0)
+
+
+def turntable_transforms(vertices, frames=91, step_deg=4.0, width=512, height=512, up=(0, 0, 1), ortho_ratio=1.2):
+    """The [F, 3, 4] float32 matrices (a host array) of `mesh_turntable`'s views, for `rasterize_mesh`: the framing of
+    the reference's viewer, in float64 on the vertices' bounding box, cast to float32 at the end.
+      * the box's centre goes to the origin and the mesh is scaled by 1 / (the box's extent along `up`);
+      * the camera is orthographic, its window `ortho_ratio` wide and ortho_ratio * height / width high (the body,
+        of height 1, fills 1 / ortho_ratio of a square image), `up` pointing up the image; at frame 0 it looks along
+        u x r, r the coordinate axis least aligned with `up`, made orthogonal to it (up = z: from -y, x to the right);
+      * frame k has the mesh turned about `up` by k * step_deg degrees;
+      * depth: the scaled mesh lies within its box's half-diagonal rho of the origin; the signed distance along the
+        viewing direction in [-rho, rho] is mapped to [0.1, 0.9], so nothing is cut by the [0, 1] depth range."""
+    if int(frames) != frames or frames < 0:
+        raise ValueError(f"turntable_transforms: frames must be an integer >= 0, got {frames}")
+    u = np.asarray(up, dtype=np.float64).reshape(-1)
+    if u.size != 3 or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
+        raise ValueError(f"turntable_transforms: up must be a non-zero direction (x, y, z), got {up!r}")
+    if not (np.isfinite(ortho_ratio) and ortho_ratio > 0):
+        raise ValueError(f"turntable_transforms: ortho_ratio must be positive, got {ortho_ratio}")
+    u = u / np.linalg.norm(u)
+    lo, hi = _bounding_box(vertices)
+    centre = 0.5 * (lo + hi)
+    extent = float(np.abs(u) @ (hi - lo))
+    scale = 1.0 / extent if extent > 0 else 1.0
+    rho = 0.5 * float(np.linalg.norm(hi - lo)) * scale
+    rho = rho if rho > 0 else 1.0
+    e = np.zeros(3)
+    e[int(np.argmin(np.abs(u)))] = 1.0
+    r = e - (e @ u) * u
+    r = r / np.linalg.norm(r)
+    view = np.cross(u, r)  # the viewing direction at frame 0: depth grows along it
+    ppu = float(width) / float(ortho_ratio)  # pixels per unit
+    K = np.array([[0, -u[2], u[1]], [u[2], 0, -u[0]], [-u[1], u[0], 0]])
+    out = np.zeros((int(frames), 3, 4))
+    for k in range(int(frames)):
+        th = np.radians(k * float(step_deg))
+        R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)  # the mesh turned about u
+        M = np.stack([ppu * r, -ppu * u, view / (2.5 * rho)]) @ R * scale  # rows: pixel x, pixel y, depth
+        out[k, :, :3] = M
+        out[k, :, 3] = np.array([0.5 * width, 0.5 * height, 0.5]) - M @ centre
+    return out.astype(_F)
+
+
+def _to_uint8_reference(image):
+    with np.errstate(invalid="ignore"):
+        x = np.rint(_F(255) * np.clip(np.nan_to_num(image.astype(_F), nan=0.0), _F(0), _F(1)))
+    return x.astype(np.uint8)
+
+
+def _turntable_colors(colors, n_vertices, who, normals):
+    """The per-vertex colours float32 [V, 3] in [0, 1]: given (uint8: c * fl(1 / 255)), or 0.5 n + 0.5 of normals()."""
+    if colors is None:
+        n = normals()
+        return n * 0.5 + 0.5
+    c = colors if isinstance(colors, torch.Tensor) else np.asarray(colors)
+    if tuple(c.shape) != (n_vertices, 3):
+        raise ValueError(f"{who}: colors of shape {tuple(c.shape)} for {n_vertices} vertices ([V, 3] wanted)")
+    if c.dtype in (torch.uint8, np.uint8):
+        # (times fl(1 / 255), not a division: a product is rounded the same way everywhere; rint(255 x) gives c back)
+        return (c.to(torch.float32) if isinstance(c, torch.Tensor) else c.astype(_F)) * float(_F(1.0 / 255.0))
+    return c
+
+
+@torch.no_grad()
+def mesh_turntable(vertices, triangles, colors=None, frames=91, step_deg=4.0, width=512, height=512, up=(0, 0, 1),
+                   ortho_ratio=1.2, background=1.0):
+    """The reference viewer's turntable of a mesh, on the device: uint8 [F, H, W, 3] (a device tensor), frame k the
+    mesh turned about `up` by k * step_deg degrees in `turntable_transforms`' framing (91 frames of 4 degrees: the
+    viewer's 0 .. 360).  `colors`: None colours by normal, 0.5 * vertex_normals(vertices, triangles) + 0.5 as the
+    viewer does (the normals of the mesh as given, computed once: the colours turn with the mesh, where the viewer
+    recomputes them in every frame's camera space); or float [V, 3] in [0, 1], or uint8 [V, 3] (extract_mesh's
+    attrs["colors"], a PLY's), used as given.  `background`: one value or three, in [0, 1].  A float image x becomes
+    rint(255 clamp(x, 0, 1)).  One rasterize_mesh (anerf_mesh_raster) per frame on the current stream; the only host
+    read is the bounding box.  Writing the frames to image files is left to the caller."""
+    v = torch.as_tensor(vertices)
+    _check_vertices(tuple(v.shape), "mesh_turntable")
+    nv = int(v.shape[0])
+    t = _device_triangles(triangles, nv, "mesh_turntable")
+    dev = t.device
+    width, height = int(width), int(height)
+    with torch.cuda.device(dev):
+        p = v.to(dev, torch.float32).contiguous()
+        c = _turntable_colors(colors, nv, "mesh_turntable", lambda: _vertex_normals(p, t))
+        c = torch.as_tensor(c).to(dev, torch.float32).contiguous()
+        Ts = turntable_transforms(p, frames, step_deg, width, height, up, ortho_ratio)
+        A0, nch, bg = _raster_args((nv, 3), np.zeros((3, 4), _F), width, height, (nv, 3), background, "mesh_turntable")
+        need = _lib.workspace("anerf_mesh_raster_workspace", nv, int(t.shape[0]), width, height)
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        out = torch.empty((len(Ts), height, width, 3), device=dev, dtype=torch.uint8)
+        for k in range(len(Ts)):
+            img = _raster_launch(p, t, np.ascontiguousarray(Ts[k]), width, height, c, nch, bg, ws).image
+            out[k] = torch.round(torch.nan_to_num(img, nan=0.0).clamp_(0.0, 1.0).mul_(255.0)).to(torch.uint8)
+    return out
+
+
+def mesh_turntable_reference(vertices, triangles, colors=None, frames=91, step_deg=4.0, width=512, height=512,
+                             up=(0, 0, 1), ortho_ratio=1.2, background=1.0):
+    """NumPy implementation of `mesh_turntable` on the checkers: uint8 [F, H, W, 3] as an array."""
+    p = np.ascontiguousarray(_lib.host_array(vertices), dtype=_F)
+    _check_vertices(p.shape, "mesh_turntable_reference")
+    c = _turntable_colors(None if colors is None else _lib.host_array(colors), len(p), "mesh_turntable_reference",
+                          lambda: vertex_normals_reference(p, triangles))
+    c = np.asarray(c, dtype=_F)
+    Ts = turntable_transforms(p, frames, step_deg, width, height, up, ortho_ratio)
+    out = np.zeros((len(Ts), int(height), int(width), 3), np.uint8)
+    for k in range(len(Ts)):
+        out[k] = _to_uint8_reference(rasterize_mesh_reference(p, triangles, Ts[k], width, height, c, background).image)
+    return out

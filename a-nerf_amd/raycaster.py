@@ -228,7 +228,9 @@ class RayCaster:
         keep_largest=1 returns the body without the floaters and cavity surfaces of a noisy density.
         `smooth` > 0 runs that many Taubin iterations over the filtered mesh (meshops.smooth_mesh, lam=smooth_lambda,
         mu=smooth_mu, open edges pinned) before the coordinate mapping and the colour query: the voxel staircases
-        and ripple go, the volume stays.  attrs["normals"] remain the gradient normals of the unsmoothed crossing."""
+        and ripple go, the volume stays.  attrs["normals"] remain the gradient normals of the unsmoothed crossing,
+        unless normals="faces": then they are the face-accumulated normals of the final vertices
+        (meshops.vertex_normals, the colouring of the reference's viewer), which also direct view="normal"."""
         from .isosurface import mesh_from_grid
         if colors and self._staged is not None:
             raise NotImplementedError("extract_mesh(colors=True): staged encoders (multires_bones > 0, relpos / "

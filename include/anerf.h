@@ -30,6 +30,8 @@
  *   anerf_mesh_compact_*    leaves floaters and cavities to the user: trimesh's split() on the host)
  *   anerf_mesh_adjacency_*, the vertex adjacency of that mesh as a CSR and Laplacian / Taubin smoothing over it (ABI 23;
  *   anerf_mesh_smooth       the reference leaves smoothing to the user: trimesh.smoothing.filter_taubin on the host)
+ *   anerf_mesh_vertex_normals   compute_normal of the reference's mesh viewer (face normals summed per vertex) and
+ *   anerf_mesh_raster       what its OpenGL pass draws: an orthographic view of the mesh (ABI 24)   render_mesh.py:35-54, 164-182
  *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
  *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
@@ -73,7 +75,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 23
+#define ANERF_ABI_VERSION 24
 
 enum {
     ANERF_OK = 0,
@@ -475,6 +477,57 @@ enum { ANERF_SMOOTH_TAUBIN = 1 };
 int anerf_mesh_smooth(const float* positions, int64_t n_vertices, const int32_t* offsets, const int32_t* neighbors,
                       int64_t n_neighbors, const uint8_t* pinned, int32_t iterations, float lambda, float mu,
                       int32_t flags, float* out, float* scratch, void* stream);
+
+/* ABI 24: face-accumulated vertex normals of an indexed triangle mesh (vertices float [n_vertices][3], triangles
+ * int32 [n_tri][3]) -- compute_normal of the reference's viewer, with every incident face counted (the viewer's own
+ * fancy-index add keeps one face per vertex and column).  fp32, every operation separately rounded:
+ *   face (a, b, c): e1 = p[b] - p[a], e2 = p[c] - p[a]; n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *   e1.x e2.y - e1.y e2.x); len = sqrt((n.x n.x + n.y n.y) + n.z n.z), raised to 1e-8f when below; n = n / len;
+ *   q = (int64) rint(n 2^30) per component (0 for a component that is not finite), added to the 64-bit integer
+ *   accumulators of a, b and c -- an integer sum has no order, so the result is the same on every run;
+ *   vertex: s = (float) sum 2^-30 (the conversion rounds to nearest even), then the same length, clamp and divide;
+ *   a vertex that no triangle uses gets (0, 0, 0).
+ * A triangle with an id outside [0, n_vertices) is skipped.  ws: anerf_mesh_vertex_normals_workspace(n_vertices, n_tri)
+ * bytes, 8-byte aligned (never 0 for valid counts; 0, with a message, for counts outside [0, 2^31)).
+ * Allocation-free, asynchronous on `stream`, no host read.  ANERF_EINVAL, before any HIP call, for a count outside
+ * [0, 2^31), a NULL pointer with a non-zero extent, a NULL, misaligned or short workspace. */
+size_t anerf_mesh_vertex_normals_workspace(int64_t n_vertices, int64_t n_tri);
+int anerf_mesh_vertex_normals(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                              float* normals, void* ws, size_t ws_bytes, void* stream);
+
+/* ABI 24: one orthographic (affine) view of such a mesh: per pixel the nearest triangle, its depth, barycentrics and
+ * interpolated vertex attributes.  transform: HOST float [3][4], read during the call: for p = (x, y, z)
+ * s_i = ((A[i][0] x + A[i][1] y) + A[i][2] z) + A[i][3]; s_0 is pixel x (pixel (row j, column i) has its centre at
+ * (i + 0.5, j + 0.5), row 0 at the top), s_1 pixel y downward, s_2 the depth, smaller nearer.
+ *   snap      X = (int64) rint(256 s_0), Y likewise; a triangle is dropped whole if any of its nine s is not finite or
+ *             an |s_0|, |s_1| exceeds 2^20 (every 64-bit product below then stays under 2^60);
+ *   coverage  integers only: with P = (256 i + 128, 256 j + 128), E_ab(P) = (X_b - X_a)(P_y - Y_a) - (Y_b - Y_a)(P_x - X_a),
+ *             A2 = E_01(vertex 2); A2 == 0 drops the triangle; A2 < 0 negates A2, E_12, E_20, E_01 and each edge's
+ *             (dx, dy) = (X_b - X_a, Y_b - Y_a) (both windings are drawn); covered iff for every edge E > 0, or E == 0
+ *             and (dy > 0 or (dy == 0 and dx < 0)): a centre on an edge two triangles share is drawn once;
+ *   depth     b1 = (float) E_20 / (float) A2, b2 = (float) E_01 / (float) A2, b0 = (1 - b1) - b2,
+ *             z = (b0 z0 + b1 z1) + b2 z2; the fragment is discarded unless 0 <= z <= 1 (a NaN is); -0 counts as +0;
+ *             the pixel keeps the smallest key (bits(z) << 32) | triangle id: the nearest, ties to the smaller id (one
+ *             64-bit unsigned atomic min per fragment: the result does not depend on the schedule);
+ *   resolve   an empty pixel: face_ids -1, depth +inf, bary 0, image = background; else b0, b1, b2 and z again by the
+ *             same expressions and image[c] = (b0 a0[c] + b1 a1[c]) + b2 a2[c] over attrs float [n_vertices][n_channels].
+ * Outputs (device): face_ids int32 [height][width], depth float [height][width], bary float [height][width][3], image
+ * float [height][width][n_channels] (attrs, background (HOST, n_channels floats) and image may be NULL with
+ * n_channels == 0).  A triangle whose clipped bounding box holds at most ANERF_RASTER_SMALL_PIXELS pixel centres is
+ * rasterised by the thread that set it up, a larger one by workgroups over 64 x 4 tiles of the box, from a list built
+ * and read on the device; the outputs are the same bits whichever path it took.  A triangle with an id outside
+ * [0, n_vertices) is skipped.  No perspective, no near-plane clipping, no multisampling.
+ * ws: anerf_mesh_raster_workspace(n_vertices, n_tri, width, height) bytes, 8-byte aligned (0, with a message, for
+ * counts outside [0, 2^31) or a width or height outside [1, 16384]).  One frame per call; allocation-free,
+ * asynchronous on `stream`, no host read.  ANERF_EINVAL, before any HIP call and naming the argument, for such counts
+ * or sizes, n_channels outside [0, 8], a NULL output, a NULL input with a non-zero extent, a NULL, misaligned or short
+ * workspace. */
+#define ANERF_RASTER_SMALL_PIXELS 256
+size_t anerf_mesh_raster_workspace(int64_t n_vertices, int64_t n_tri, int32_t width, int32_t height);
+int anerf_mesh_raster(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                      const float* transform, int32_t width, int32_t height, const float* attrs, int32_t n_channels,
+                      const float* background, int32_t* face_ids, float* depth, float* bary, float* image, void* ws,
+                      size_t ws_bytes, void* stream);
 
 /* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
  * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /

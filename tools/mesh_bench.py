@@ -26,6 +26,14 @@ difference to a 100-iteration call; extract_mesh_smooth_ms, extract_mesh(keep_la
 extract_mesh_keep_largest_ms.  smooth_reference_host_ms is smooth_mesh_reference (NumPy) on the same mesh, once, for
 scale; the device result is checked against it bit for bit.
 
+Looking at the body (meshops.py; csrc/anerf_raster.hip), on the same filtered mesh: vertex_normals_ms,
+meshops.vertex_normals (the id range check and three launches); raster_frame_ms, one 512 x 512 rasterize_mesh of the
+body coloured by those normals under frame 7 of turntable_transforms; raster_large_frame_ms, the same image size for a
+cube's twelve triangles (the workgroups' path: the body's triangles are a pixel or two each and take the thread's);
+turntable_ms, mesh_turntable at its defaults (91 frames of 512 x 512, normals included); raster_reference_host_ms,
+rasterize_mesh_reference (NumPy) on the body's frame, once, for scale; the device frame is checked against it bit for
+bit.
+
 Prints one JSON line, and appends it to the file given with --append (the record: profiles/mesh_bench.jsonl).
 Usage: python tools/mesh_bench.py [res] [precision] [--append FILE]"""
 import importlib
@@ -152,6 +160,34 @@ def _smooth_legs(rc, kps, skts, res, thr, v, t):
             "extract_mesh_smooth_ms": round(extract_ms, 3), "smooth_reference_host_ms": round(ref_ms, 1)}
 
 
+def _raster_legs(v, t):
+    """Normals, one frame and the turntable on the body (the mesh keep_largest=1 leaves)."""
+    v, t = meshops.filter_mesh(v, t, keep_largest=1)
+    normals_ms, nrm = _time(lambda: meshops.vertex_normals(v, t), reps=20)
+    colors = (nrm * 0.5 + 0.5).contiguous()
+    A = meshops.turntable_transforms(v, 91, 4.0, 512, 512)[7]
+    frame_ms, frame = _time(lambda: meshops.rasterize_mesh(v, t, A, 512, 512, colors), reps=20)
+    cube = torch.tensor([[x, y, z] for x in (-1., 1.) for y in (-1., 1.) for z in (-1., 1.)], device=v.device)
+    ct = torch.tensor([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6],
+                       [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]], device=v.device, dtype=torch.int32)
+    CA = meshops.turntable_transforms(cube, 91, 4.0, 512, 512, up=(0.2, 0.3, 1.0))[7]
+    large_ms, _ = _time(lambda: meshops.rasterize_mesh(cube, ct, CA, 512, 512, cube * 0.5 + 0.5), reps=20)
+    turntable_ms, frames = _time(lambda: meshops.mesh_turntable(v, t), reps=3)
+    v_host, t_host, c_host = v.cpu().numpy(), t.cpu().numpy(), colors.cpu().numpy()
+    t0 = time.perf_counter()
+    ref = meshops.rasterize_mesh_reference(v_host, t_host, A, 512, 512, c_host)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    for name in ("face_ids", "depth", "bary", "image"):
+        g, r = getattr(frame, name).cpu().numpy(), getattr(ref, name)
+        assert np.array_equal(g.view(np.int32), r.view(np.int32)), name
+    nref = meshops.vertex_normals_reference(v_host, t_host)
+    assert np.array_equal(nrm.cpu().numpy().view(np.int32), nref.view(np.int32))
+    return {"vertex_normals_ms": round(normals_ms, 3), "raster_frame_ms": round(frame_ms, 3),
+            "raster_covered_pixels": int((frame.face_ids >= 0).sum()), "raster_large_frame_ms": round(large_ms, 3),
+            "turntable_ms": round(turntable_ms, 3), "turntable_frames": int(frames.shape[0]),
+            "raster_reference_host_ms": round(ref_ms, 1)}
+
+
 def main():
     argv = list(sys.argv[1:])
     append = None
@@ -179,6 +215,7 @@ def main():
     _, ti, ni = iso.isosurface(grid, thr, relu=True, normals=True)
     legs = _filter_legs(rc, kps, skts, res, thr, v, ti, ni)
     legs.update(_smooth_legs(rc, kps, skts, res, thr, v, ti))
+    legs.update(_raster_legs(v, ti))
     n = (res + 1) ** 3
     line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
                       "grid_ms": round(grid_ms, 3), "isosurface_ms": round(iso_ms, 3),
