@@ -9,6 +9,8 @@ their own dependencies (anerf_gemm.hip reads only include/anerf.h; anerf_iso.hip
 anerf_raster.hip that and csrc/anerf_scan.hpp, which no other unit reads, anerf_iso.hip also its case table), then
 link into the library: an edit of the training GEMMs, of the iso-surface, of the mesh or of the raster kernels
 recompiles one unit, an edit of their shared scan header those three, never the render kernels' instances.
+The render kernels are two units over the same headers: anerf_render_f16.hip holds the fp16 instances of the three MLP
+kernels and is the only unit compiled with RENDER_F16_FLAGS (MFMA results in VGPRs), anerf_render.hip everything else.
 """
 import hashlib
 import os
@@ -19,7 +21,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "anerf.h")
-SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_gemm.hip"),
+SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_render_f16.hip"),
+       os.path.join(CSRC, "anerf_gemm.hip"),
        os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip"),
        os.path.join(CSRC, "anerf_raster.hip")]
 SCAN_HEADER = os.path.join(CSRC, "anerf_scan.hpp")  # anerf_iso.hip's, anerf_mesh.hip's and anerf_raster.hip's alone
@@ -30,11 +33,18 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared",
          "-Wno-unused-result"]
 CFLAGS = [f for f in FLAGS if f != "-shared"]
+# anerf_render_f16.hip alone: the fp16 layers' scale, relu and split run on the VALU, which cannot read AGPRs
+# (tools/build_ab.sh and tools/build_stamps.sh compile that unit with the same option)
+RENDER_F16_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+UNIT_FLAGS = {"anerf_render_f16.hip": RENDER_F16_FLAGS}
 
 
 def _hash(files, extra=""):
     h = hashlib.sha256()
     h.update((" ".join(FLAGS) + extra).encode())
+    for name in sorted(UNIT_FLAGS):  # (of the units among `files`: every one for the library's stamp)
+        if any(os.path.basename(d) == name for d in files):
+            h.update((name + " " + " ".join(UNIT_FLAGS[name])).encode())
     for d in files:
         if os.path.isfile(d):
             h.update(os.path.basename(d).encode())
@@ -44,7 +54,7 @@ def _hash(files, extra=""):
 
 
 def source_hash():
-    """sha256 over the flags and the bytes of csrc/* + include/anerf.h (sorted by name)."""
+    """sha256 over the flags, the units' own flags and the bytes of csrc/* + include/anerf.h (sorted by name)."""
     deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC))
     deps.append(HEADER)
     return _hash(deps)
@@ -52,8 +62,8 @@ def source_hash():
 
 def unit_deps(src):
     """The files a translation unit reads: anerf_gemm.hip only the C header; anerf_mesh.hip, anerf_raster.hip and
-    anerf_iso.hip the scan header and the C header, anerf_iso.hip its case table as well; anerf_render.hip every other
-    csrc header."""
+    anerf_iso.hip the scan header and the C header, anerf_iso.hip its case table as well; anerf_render.hip and
+    anerf_render_f16.hip every other csrc header."""
     name = os.path.basename(src)
     if name == "anerf_gemm.hip":
         return [src, HEADER]
@@ -80,7 +90,7 @@ def _object(src, verbose, force=False):
     if os.path.exists(obj) and not force:
         return obj
     tmp = obj + ".tmp"
-    cmd = [HIPCC] + CFLAGS + ["-c", "-o", tmp, src]
+    cmd = [HIPCC] + CFLAGS + UNIT_FLAGS.get(os.path.basename(src), []) + ["-c", "-o", tmp, src]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -1,5 +1,5 @@
 // anerf_mlp.hpp — MFMA building blocks of the fused MLP: weight ring, dense layer with fused boundary, encoder k-streams (bone directions, windowed joints), view-direction part, trunk and one 32-sample block.
-// Part of the single translation unit anerf_render.hip (included there, in order).
+// Included, in order, by anerf_render.hip and by anerf_render_f16.hip (the fp16 instances' unit).
 #pragma once
 
 // ======================================================================= MLP building blocks
@@ -433,6 +433,21 @@ struct H3T {
 
 __device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (e + 127) << 23); }  // |e| <= 126
 
+// A commutative reduction of a lane's value with lane ^ 32's, the same in both lanes.  v_permlane32_swap_b32
+// (gfx950) exchanges the upper half of its first operand with the lower half of its second in the VALU: of two
+// copies of x, one then holds the lower half's values in both halves and the other the upper half's.  __shfl_xor(x, 32)
+// is a ds_bpermute_b32, an LDS round trip plus its address register; between two fp16 layers that latency is exposed.
+__device__ __forceinline__ int max_halves(int x) {
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+    return max((int)r[0], (int)r[1]);
+}
+__device__ __forceinline__ float sum_halves(float x) {  // x + the other half's x, as x + __shfl_xor(x, 32)
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const unsigned lo = r[0], hi = r[1];  // (through scalars: see h3_scale on bit casts of vector elements)
+    return __builtin_bit_cast(float, lo) + __builtin_bit_cast(float, hi);
+}
+
 // values a, b (relu'd, in the input's units) times t -> dword q of the two fp16 components: the high
 // part rounds x to 11 significant bits in the f32 encoding (exact in fp16), the low part is the
 // exact remainder rounded to nearest even (v_cvt_pk_f16_f32), so x0 + x1 is within 2^-23 |x| of x
@@ -463,7 +478,8 @@ __device__ __forceinline__ void split2_block_pair(const f32x16& hb, float t, H3T
 // (NP = 3: fp16x3, NP = 4: fp16x4)
 constexpr int H3_NLG = 2;  // (experiments: MFMAs followed by loads, loads after each; NLG x NL = 4)
 // VALU per MFMA gap in the lead groups (input copies + bias initialisation; round 5 A/B: 4 +0.2 % over 2, 6 -0.2 %,
-// profiles/r05e_ab.txt)
+// profiles/r05e_ab.txt; again with the accumulators in VGPRs and the half-wave reductions in the VALU: 2 and 4 within
+// 0.05 %, 6 -1.2 %, and H3_IL 1 / 3 no better than 2, profiles/f16_vgpr_form_ab.txt)
 constexpr int H3_LEAD_IL = 4;
 template <int NP, int NV = H3_IL>
 __device__ __forceinline__ void h3_group_schedule() {
@@ -505,7 +521,7 @@ __device__ __forceinline__ float h3_scale(const f32x16 (&a)[RBI], int& es, int e
             const float v = a[rb][i];
             m = max(m, __builtin_bit_cast(int, v));
         }
-    m = max(m, __shfl_xor(m, 32));
+    m = max_halves(m);
     int shift = m > 0 ? top - (m >> 23) : 0;  // (m >> 23: the biased exponent; top = 127 + 10)
     // (cap: the skip layer's h part keeps its output units at most 2^cap, so that the fp16 x parts'
     // features, scaled into those units, stay in range: enc16_units)
@@ -535,11 +551,17 @@ __device__ __forceinline__ void mlp_layer_h3(f32x16 (&out)[RBO], f32x16 (&ain)[R
     const __amdgpu_buffer_rsrc_t rn = make_rsrc(next ? next : wp);
     const float t = h3_scale<RBI>(ain, es, ew, top, cap);
     const float S = pow2f(es);
+    // The lane's wave half for the bias rows, formed here by one VALU instruction from nothing that is live (bit 31 of
+    // the lower lane mask counted among the lanes below this one: 0 in lanes 0-31, 1 in lanes 32-63), in every
+    // layer (volatile: not hoisted): a bias row address kept from one layer to the next lives across the MFMA run,
+    // where the allocator parks it in an AGPR, and comes back by a v_accvgpr_read_b32 between the layers
+    int hb = 0;
+    if constexpr (OUT_SAME) asm volatile("v_mbcnt_lo_u32_b32 %0, %1, 0" : "=v"(hb) : "s"(0x80000000u));
     auto convert_half = [&](int rb, int half) {  // relu of 8 inputs (+ their 8 scaled bias outputs)
 #pragma unroll
         for (int i = 8 * half; i < 8 * half + 8; ++i) h[rb][i] = relu_act(ain[rb][i]);
         if (OUT_SAME && rb < RBO) {
-            const f32x4* p = reinterpret_cast<const f32x4*>(bias + (rb * 2 + hh) * 16 + 8 * half);
+            const f32x4* p = reinterpret_cast<const f32x4*>(bias + (rb * 2 + hb) * 16 + 8 * half);
             const f32x4 v0 = p[0], v1 = p[1];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1588,7 +1610,9 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
         mlp_layer<RBV, RB, true, false, true>(av, acc, h, nullptr, net.wview, lane, ring, nullptr,
                                               bias + (M.D + 1) * W, sig);
     STAMP(st, 16);
-    sig += __shfl_xor(sig, 32);
+    // (the fp16 modes: in the VALU; the other modes' instances keep the code they were measured with)
+    if constexpr (P >= 3) sig = sum_halves(sig);
+    else sig += __shfl_xor(sig, 32);
     sig += net.balpha;
     const int vsteps = view_dir_part<RBV>(av, M, G, wvp, reinterpret_cast<const unsigned*>(ray) + 12, lane,
                                           P >= 3 ? pow2f(es) : 1.0f);
@@ -1602,7 +1626,8 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
         for (int rb = 0; rb < RBV; ++rb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) a += wr[rb * 16 + i] * relu_act(av[rb][i]);
-        a += __shfl_xor(a, 32);
+        if constexpr (P >= 3) a = sum_halves(a);
+        else a += __shfl_xor(a, 32);
         if constexpr (P >= 3) a *= pow2f(-es);  // (the view layer's units)
         rgb[c] = a + net.brgb[c];
     }

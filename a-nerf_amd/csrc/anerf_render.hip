@@ -11,12 +11,14 @@
 // split into a per-ray matrix G[j][n] (computed once per ray in LDS) and the per-sample cutoff
 // weights w'_j, so the per-sample K of the view layer is W + NJ + 1 instead of W + 27 NJ.
 //
-// Source layout (one translation unit, included in this order):
+// Source layout (included in this order):
 //   anerf_device.hpp   numerics helpers (torch/numpy-faithful sums, linspace, sincos, relu)
 //   anerf_types.hpp    device model / launch structs, LDS plan, diagnostic stamps
 //   anerf_mlp.hpp      MFMA building blocks: weight ring, dense layer, encoder streams, trunk
 //   anerf_stages.hpp   per-ray stages: view factor G, compositing, importance sampling
-//   anerf_kernels.hpp  __global__ kernels (render, density, near/far, rays, compose, encode)
+//   anerf_kernels.hpp  templated __global__ kernels (render, density, radiance); their fp16 instances are
+//                      compiled in anerf_render_f16.hip (MFMA results in VGPRs) and extern here
+//   anerf_kernels_small.hpp  the small __global__ kernels (near/far, rays, compose, encode)
 //   anerf_pose.hpp     pose -> skeleton transforms (kinematic chain, inverse)
 //   anerf_boxes.hpp    bounding cylinder + 2-D pixel box per frame (kp_to_valid_rays)
 //   anerf_pack.hpp     host weight packing / model binding
@@ -46,6 +48,8 @@ using namespace anerf;
 #include "anerf_mlp.hpp"
 #include "anerf_stages.hpp"
 #include "anerf_kernels.hpp"
+ANERF_F16_INSTANCES(extern)
+#include "anerf_kernels_small.hpp"
 #include "anerf_train.hpp"
 #include "anerf_trainfwd.hpp"
 #include "anerf_pose.hpp"

@@ -1,5 +1,5 @@
 // anerf_stages.hpp — per-ray stages: view factor G, compositing (raw2outputs), importance sampling + merge, bias staging.
-// Part of the single translation unit anerf_render.hip (included there, in order).
+// Included, in order, by anerf_render.hip and by anerf_render_f16.hip (the fp16 instances' unit).
 #pragma once
 
 // ======================================================================= per-ray stages

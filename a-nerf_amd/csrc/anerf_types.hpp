@@ -1,5 +1,5 @@
 // anerf_types.hpp — device-side model / launch argument structs, diagnostic stamps, LDS plan.
-// Part of the single translation unit anerf_render.hip (included there, in order).
+// Included, in order, by anerf_render.hip and by anerf_render_f16.hip (the fp16 instances' unit).
 #pragma once
 
 
