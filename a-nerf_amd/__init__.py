@@ -10,8 +10,9 @@ from .raycaster import RayCaster, create_raycaster, load_checkpoint
 from .render import batchify_rays, render, render_path, render_frames
 from .isosurface import isosurface, isosurface_reference, mesh_from_grid, read_ply, render_mesh, write_ply
 from .meshops import (filter_mesh, mesh_components, mesh_components_reference, mesh_turntable, rasterize_mesh,
-                      rasterize_mesh_reference, smooth_mesh, smooth_mesh_reference, turntable_transforms,
-                      vertex_adjacency, vertex_adjacency_reference, vertex_normals, vertex_normals_reference)
+                      rasterize_mesh_reference, simplify_mesh, simplify_mesh_reference, smooth_mesh,
+                      smooth_mesh_reference, turntable_transforms, vertex_adjacency, vertex_adjacency_reference,
+                      vertex_normals, vertex_normals_reference, SimplifiedMesh, SIMPLIFY_MAX_CELLS)
 from . import dataset, rays, synthetic, train
 from .dataset import RayImageDataset, RayImageSampler
 
@@ -21,4 +22,5 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "mesh_components", "mesh_components_reference", "filter_mesh", "vertex_adjacency",
            "vertex_adjacency_reference", "smooth_mesh", "smooth_mesh_reference", "vertex_normals",
            "vertex_normals_reference", "rasterize_mesh", "rasterize_mesh_reference", "mesh_turntable",
-           "turntable_transforms"]
+           "turntable_transforms", "simplify_mesh", "simplify_mesh_reference", "SimplifiedMesh",
+           "SIMPLIFY_MAX_CELLS"]

@@ -38,7 +38,8 @@ ANERF_ENC_KP_QUERYPTS = 64  # --kp_dist_type querypts (staged, ABI 15)
 ANERF_ENC_VIEW_WINDOWS = 128  # training layout: the view part as the NJ view windows (ABI 16)
 ANERF_SMOOTH_TAUBIN = 1  # anerf_mesh_smooth's flags: a step with mu after every step with lambda
 ANERF_RASTER_SMALL_PIXELS = 256  # include/anerf.h: the clipped bounding box up to which a triangle's own thread draws it
-ABI_VERSION = 24  # include/anerf.h ANERF_ABI_VERSION: the structs below
+ANERF_SIMPLIFY_MAX_CELLS = 1 << 26  # include/anerf.h: the cells anerf_mesh_simplify_*'s table may have
+ABI_VERSION = 25  # include/anerf.h ANERF_ABI_VERSION: the structs below
 
 
 class ModelDesc(ctypes.Structure):
@@ -185,6 +186,14 @@ SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
+    "anerf_mesh_simplify_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "anerf_mesh_simplify_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "anerf_mesh_simplify_emit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "anerf_radiance_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),

@@ -286,7 +286,7 @@ def read_ply(path, attributes=False):
 
 def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False, normals=False, colors=False,
                    view="normal", cams=None, radiance=None, keep_largest=None, min_triangles=0, smooth=0,
-                   smooth_lambda=0.5, smooth_mu=-0.53):
+                   smooth_lambda=0.5, smooth_mu=-0.53, simplify=None):
     """extract_mesh's second half: the iso-surface of a caster's render_mesh_density grid (relu on load, as
     run_render.render_mesh's np.maximum(raw_d, 0)) in the requested coordinates:
       "index"  array-index coordinates, as mcubes.marching_cubes;
@@ -314,7 +314,13 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     `normals="faces"`: attrs["normals"] are instead the face-accumulated normals (meshops.vertex_normals, the
     colouring of the reference's viewer) of the FINAL vertices -- after the filter, the smoothing and the `coords`
     mapping, for the winding returned -- and with view="normal" these give the view directions of the colour query;
-    the grid's gradient is not evaluated.  normals=True / False behave as before."""
+    the grid's gradient is not evaluated.  normals=True / False behave as before.
+    `simplify`: a cell edge in voxels (> 0) runs meshops.simplify_mesh (vertex clustering) after the component filter
+    and the smoothing, in index coordinates with origin (0, 0, 0) -- the cells are blocks of voxels, the same ones for
+    every frame of a sequence -- and before the `coords` mapping and the colour query: colours are queried at the
+    simplified vertices only.  The gradient normals are gathered by representative (a new vertex takes the normal of
+    its cell's first vertex); normals="faces" are computed on the final, simplified mesh.  With simplify=None that
+    code is not entered."""
     if coords not in ("unit", "index", "world"):
         raise ValueError(f"coords must be 'unit', 'index' or 'world', got {coords!r}")
     one_dir = None
@@ -344,6 +350,12 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
     if smooth != 0:  # (a negative count is smooth_mesh's ValueError)
         from .meshops import smooth_mesh
         v = smooth_mesh(v, t, iterations=smooth, lam=smooth_lambda, mu=smooth_mu, pin="boundary")
+    if simplify is not None:  # (a cell that is not > 0 is simplify_mesh's ValueError)
+        from .meshops import simplify_mesh
+        simple = simplify_mesh(v, t, simplify, attrs=None if n is None else [n], origin=(0.0, 0.0, 0.0))
+        v, t = simple.vertices, simple.triangles
+        if n is not None:
+            (n,) = simple.attrs
     vi = v
     kp0 = torch.as_tensor(kps).to(v.device, torch.float32).reshape(-1, 3)[0]
 
@@ -387,7 +399,7 @@ def mesh_from_grid(grid, kps, radius, res, threshold, coords="unit", flip=False,
 @torch.no_grad()
 def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, res=255, threshold=10.,
                 normals=False, colors=False, view="normal", keep_largest=None, min_triangles=0, smooth=0,
-                smooth_lambda=0.5, smooth_mu=-0.53):
+                smooth_lambda=0.5, smooth_mu=-0.53, simplify=None):
     """Drop-in for run_render.render_mesh (run_render.py:970-986): per pose, the density grid and its iso-surface
     on the device, written to basedir/meshes/{i:03d}.ply in the reference's vertices / res - .5 coordinates.
     Returns the list of (vertices, triangles) device tensors (the reference builds that list and drops it).
@@ -396,7 +408,8 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, re
     red / green / blue) and the list holds (vertices, triangles, attrs).  `keep_largest` / `min_triangles`: the
     component filter of RayCaster.extract_mesh (keep_largest=1: the body without floaters).  `smooth` /
     `smooth_lambda` / `smooth_mu`: its Taubin smoothing, after the filter; the PLYs hold the smoothed vertices, and
-    their normals stay the gradient normals of the unsmoothed crossing."""
+    their normals stay the gradient normals of the unsmoothed crossing.  `simplify`: its vertex clustering (a cell edge
+    in voxels), after the smoothing; the PLYs hold the simplified mesh."""
     ray_caster = render_kwargs["ray_caster"]
     os.makedirs(os.path.join(basedir, "meshes"), exist_ok=True)
     kps, skts, bones = tensor_data["kp"], tensor_data["skts"], tensor_data["bones"]
@@ -405,6 +418,8 @@ def render_mesh(basedir, render_kwargs, tensor_data, chunk=1024, radius=1.80, re
              if (keep_largest is not None or min_triangles > 0) else {})
     if smooth != 0:
         keeps.update(smooth=smooth, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
+    if simplify is not None:
+        keeps.update(simplify=simplify)
     v_t_tuples = []
     for i in range(len(kps)):
         out = ray_caster.extract_mesh(kps[i:i + 1], skts[i:i + 1], None if bones is None else bones[i:i + 1],

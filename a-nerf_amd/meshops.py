@@ -41,6 +41,31 @@ do it on the device, csrc/anerf_raster.hip; their contract, shared with `vertex_
 DESIGN.md: quantised face normals summed as 64-bit integers; coverage on vertices snapped to 1 / 256 pixel with
 integer edge functions and a tie rule; a depth test that is one 64-bit atomic min per fragment.  Orthographic / affine
 cameras only: no perspective, no near-plane clipping, no multisampling, and no image files are written.
+
+The extracted mesh is as dense as the grid (two triangles per surface voxel), and whoever takes it further decimates it
+first; the reference leaves that to trimesh, which needs open3d or fast_simplification for it.  `simplify_mesh` is
+vertex clustering (Rossignac-Borrel) on the device, csrc/anerf_simplify.hip (anerf_mesh_simplify_count,
+anerf_mesh_simplify_emit): one pass of integer decisions.  Its contract, shared with `simplify_mesh_reference` (the
+NumPy checker, reached only by that name), for vertices fp32 [V, 3], triangles int32 [T, 3], a cell edge `cell` > 0
+(fp32), an origin o (fp32 [3]) and dims (n0, n1, n2) with n0 n1 n2 <= SIMPLIFY_MAX_CELLS = 2^26; every fp32 operation
+is separately rounded, divisions are correctly rounded:
+  * the cell of a vertex: q_a = (p_a - o_a) / cell, c_a = floor(q_a); the vertex is valid iff all three q_a are finite
+    and 0 <= c_a < n_a; its key is (c0 n1 + c1) n2 + c2;
+  * a cell's representative is its valid member with the smallest vertex id; the new vertices are the representatives
+    in ascending original id (the relative order is kept, as in filter_mesh); vertex_map[v] is the new id of v's
+    cell, or -1 for a vertex that is not valid; representatives[j] is the original id of new vertex j;
+  * the position of a new vertex is the fixed-point mean of its cell's members, which does not depend on the order of
+    arrival: r_a = q_a - float(c_a) (exact in fp32), i_a = rint(r_a 2^20) as int64, S_a the 64-bit integer sum of
+    i_a over the members (below 2^51), n their number; m_a = float(double(S_a) / double(n) 2^-20);
+    p'_a = o_a + cell (float(c_a) + m_a);
+  * a triangle (a, b, c) maps to (a', b', c') through vertex_map and is dropped if an id is outside [0, V), a mapped
+    id is -1, two mapped ids are equal, or an earlier surviving triangle (a smaller original index) has the same
+    unordered set {a', b', c'}, in either winding; the survivors keep their relative order and their own vertex
+    order, neither rotated nor re-wound;
+  * integers, or a fixed order of roundings, throughout: the same bits on every run and under any schedule.
+Out of scope: quadric-error placement, edge-collapse decimation, target triangle counts, and keeping the result
+manifold -- clustering can pinch thin parts into edges that more than two triangles share (it does on a random field's
+surface; closed, well-separated surfaces such as a sphere or a torus stay closed).
 """
 import collections
 import ctypes
@@ -53,6 +78,9 @@ from . import _lib
 MeshComponents = collections.namedtuple("MeshComponents", ["labels", "roots", "triangle_counts", "vertex_counts"])
 VertexAdjacency = collections.namedtuple("VertexAdjacency", ["offsets", "neighbors", "boundary"])
 MeshRaster = collections.namedtuple("MeshRaster", ["face_ids", "depth", "bary", "image"])
+SimplifiedMesh = collections.namedtuple("SimplifiedMesh",
+                                        ["vertices", "triangles", "vertex_map", "representatives", "attrs"])
+SIMPLIFY_MAX_CELLS = _lib.ANERF_SIMPLIFY_MAX_CELLS  # the cells of simplify_mesh's grid at most (include/anerf.h)
 # the clipped bounding box (in pixel centres) up to which the thread that set a triangle up also draws it
 # (include/anerf.h; larger boxes are drained by workgroups -- the outputs are the same bits either way)
 RASTER_SMALL_PIXELS = _lib.ANERF_RASTER_SMALL_PIXELS
@@ -171,14 +199,14 @@ def _kept_components(triangle_counts, keep_largest, min_triangles):
     return ok
 
 
-def _gather_attrs(attrs, gather, n_vertices):
+def _gather_attrs(attrs, gather, n_vertices, who="filter_mesh"):
     if attrs is None:
         return None
     items = attrs.items() if isinstance(attrs, dict) else enumerate(attrs)
     out = {}
     for k, a in items:
         if a.shape[0] != n_vertices:
-            raise ValueError(f"filter_mesh: attribute {k!r} has {a.shape[0]} rows for {n_vertices} vertices")
+            raise ValueError(f"{who}: attribute {k!r} has {a.shape[0]} rows for {n_vertices} vertices")
         out[k] = gather(a)
     return out if isinstance(attrs, dict) else [out[i] for i in range(len(out))]
 
@@ -809,3 +837,200 @@ def mesh_turntable_reference(vertices, triangles, colors=None, frames=91, step_d
     for k in range(len(Ts)):
         out[k] = _to_uint8_reference(rasterize_mesh_reference(p, triangles, Ts[k], width, height, c, background).image)
     return out
+
+
+# ------------------------------------------------------------------ vertex clustering
+def _simplify_args(vertices_shape, triangles, cell, origin, attrs, who):
+    """The argument errors of simplify_mesh and its checker that need no look at the data: (cell float32, the given
+    origin float32 [3] or None)."""
+    _check_vertices(vertices_shape, who)
+    shape = tuple(triangles.shape)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{who}: triangles must be [T, 3], got shape {shape}")
+    if str(triangles.dtype).split(".")[-1] not in ("int32", "int64"):  # (a tensor's or an array's)
+        raise ValueError(f"{who}: triangles must be int32 or int64, got {triangles.dtype}")
+    nv = vertices_shape[0]
+    if nv > 0x7fffffff or shape[0] > 0x7fffffff:
+        raise ValueError(f"{who}: {nv} vertices / {shape[0]} triangles do not fit int32 ids")
+    with np.errstate(all="ignore"):
+        c = _F(cell)
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError(f"{who}: cell must be finite and > 0 (as float32), got {cell}")
+    o = None
+    if origin is not None:
+        o = np.ascontiguousarray(_lib.host_array(origin), dtype=_F).reshape(-1)
+        if o.size != 3 or not np.isfinite(o).all():
+            raise ValueError(f"{who}: origin must be three finite values (x, y, z), got {origin!r}")
+    _gather_attrs(attrs, lambda a: None, nv, who)  # (the row counts)
+    return c, o
+
+
+def _simplify_grid(lo, hi, finite, tri_lo, tri_hi, n_vertices, cell, origin, who):
+    """The errors that need the one look at the data (the vertices' per-axis minimum and maximum, whether all are
+    finite, the smallest and largest triangle id or None), and the grid: (origin float32 [3], dims int32 [3])."""
+    if tri_lo is not None and (tri_lo < 0 or tri_hi >= n_vertices):
+        raise ValueError(f"{who}: vertex ids span [{int(tri_lo)}, {int(tri_hi)}], outside [0, {n_vertices})")
+    if not finite:
+        raise ValueError(f"{who}: the vertices must be finite, found a NaN or infinite coordinate")
+    lo, hi = np.asarray(lo, dtype=_F), np.asarray(hi, dtype=_F)
+    o = lo if origin is None else origin
+    if (lo < o).any():
+        raise ValueError(f"{who}: a vertex lies below the origin {tuple(float(x) for x in o)}: the minimum is "
+                         f"{tuple(float(x) for x in lo)}")
+    with np.errstate(all="ignore"):
+        top = np.floor((hi - o) / cell)  # float32, the arithmetic of the contract: the largest cell index per axis
+    cells = 1
+    for x in top:
+        cells = cells * (int(x) + 1) if np.isfinite(x) and cells <= SIMPLIFY_MAX_CELLS else SIMPLIFY_MAX_CELLS + 1
+    if cells > SIMPLIFY_MAX_CELLS:
+        raise ValueError(f"{who}: cells of {float(cell)} over the extent {tuple(float(x) for x in hi - o)} are more "
+                         f"than SIMPLIFY_MAX_CELLS = {SIMPLIFY_MAX_CELLS} (2^26): use a larger cell")
+    return np.ascontiguousarray(o, dtype=_F), np.ascontiguousarray(top.astype(np.int32) + 1)
+
+
+def _simplify_count(p, t, origin, cell, dims, ws, totals):
+    """anerf_mesh_simplify_count on checked device tensors (ws: its workspace; totals int64 [2] on the device)."""
+    _lib.check(_lib.load().anerf_mesh_simplify_count(
+        _lib.ptr(p), int(p.shape[0]), _lib.ptr(t), int(t.shape[0]), origin.ctypes.data_as(ctypes.c_void_p),
+        float(cell), dims.ctypes.data_as(ctypes.c_void_p), _lib.ptr(ws), int(ws.shape[0]), _lib.ptr(totals),
+        _lib.stream_handle(p.device)), "anerf_mesh_simplify_count")
+
+
+def _simplify_emit(p, t, origin, cell, dims, ws, out_v, out_t, vertex_map, reps):
+    """anerf_mesh_simplify_emit after _simplify_count on the same arguments, into outputs of the counted sizes."""
+    _lib.check(_lib.load().anerf_mesh_simplify_emit(
+        _lib.ptr(p), int(p.shape[0]), _lib.ptr(t), int(t.shape[0]), origin.ctypes.data_as(ctypes.c_void_p),
+        float(cell), dims.ctypes.data_as(ctypes.c_void_p), _lib.ptr(ws), int(ws.shape[0]), _lib.ptr(out_v),
+        int(out_v.shape[0]), _lib.ptr(out_t), int(out_t.shape[0]), _lib.ptr(vertex_map), _lib.ptr(reps),
+        _lib.stream_handle(p.device)), "anerf_mesh_simplify_emit")
+
+
+def _simplify_workspace(n_vertices, n_tri, dims, device):
+    need = _lib.workspace("anerf_mesh_simplify_workspace", int(n_vertices), int(n_tri),
+                          int(dims[0]) * int(dims[1]) * int(dims[2]))
+    return torch.empty(need, device=device, dtype=torch.uint8)
+
+
+@torch.no_grad()
+def simplify_mesh(vertices, triangles, cell, attrs=None, origin=None):
+    """Simplify a mesh (vertices float [V, 3], triangles int [T, 3]) by vertex clustering on the device: the vertices
+    are snapped to a grid of cubic cells of edge `cell` that starts at `origin`, every cell's vertices become one (at
+    their fixed-point mean), and the triangles that collapse, or that repeat the vertex set of an earlier one in
+    either winding, are dropped.  Returns SimplifiedMesh of device tensors:
+      vertices float32 [V', 3], triangles int32 [T', 3]   the new mesh, both in their original relative order;
+      vertex_map int32 [V]                                the new id of every old vertex;
+      representatives int32 [V']                          the old id of every new vertex: its cell's smallest;
+      attrs                                               `attrs` (a dict or list of per-vertex tensors [V, ...]; None
+                                                          gives None) gathered with `representatives`, exactly as
+                                                          filter_mesh gathers with its kept index: a new vertex takes
+                                                          its representative's normal or colour, nothing is averaged.
+    origin=None: the per-axis fp32 minimum of the vertices; a given origin (x, y, z) keeps the cells where they are from
+    one mesh to the next (extract_mesh clusters in index coordinates from (0, 0, 0): cells aligned with the voxels).
+    The grid's dims follow from the per-axis maximum.  The contract is the module docstring's, bit for bit that of
+    `simplify_mesh_reference`.
+    Two host reads: the minimum, the maximum, the finiteness of the vertices and the range of the ids in one; the two
+    totals between anerf_mesh_simplify_count and anerf_mesh_simplify_emit in the other.  Everything runs on the current
+    stream.  ValueError before anything is launched: a non-finite vertex; a cell that is not finite or <= 0; a vertex
+    below a given origin; more than SIMPLIFY_MAX_CELLS = 2^26 cells; ids outside [0, V); attrs whose row count is not V.
+    Stricter than the C entries, which drop a vertex outside the grid or a triangle with an id outside [0, V) silently.
+    Without vertices the result is empty; without triangles the vertices are still clustered.  Out of scope (module
+    docstring): quadric-error placement, edge collapses, target triangle counts, keeping the result manifold."""
+    who = "simplify_mesh"
+    v, t = torch.as_tensor(vertices), torch.as_tensor(triangles)
+    cell, origin = _simplify_args(tuple(v.shape), t, cell, origin, attrs, who)
+    nv, nt = int(v.shape[0]), int(t.shape[0])
+    dev = v.device if v.is_cuda else (t.device if t.is_cuda else None)
+    vf = v.to(torch.float32)
+    if nv == 0:
+        lo = hi = np.zeros(3, _F)
+        stats = [1.0] + ([float(t.amin()), float(t.amax())] if nt else [])  # (ids without vertices: an error)
+    else:
+        parts = [vf.amin(0).double(), vf.amax(0).double(), torch.isfinite(vf).all().double().reshape(1)]
+        if nt:  # (ids below 2^31 are exact in float64)
+            parts += [t.amin().double().reshape(1).to(vf.device), t.amax().double().reshape(1).to(vf.device)]
+        stats = torch.cat(parts).cpu().numpy()  # (the first host read: put together where the vertices are)
+        lo, hi, stats = stats[0:3], stats[3:6], stats[6:]
+    o, dims = _simplify_grid(lo, hi, bool(stats[0]), stats[1] if nt else None, stats[2] if nt else None, nv, cell,
+                             origin, who)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        if nv == 0:
+            empty_v = torch.zeros((0, 3), device=dev, dtype=torch.float32)
+            empty_i = torch.zeros(0, device=dev, dtype=torch.int32)
+            out_a = _gather_attrs(attrs, lambda a: torch.as_tensor(a).to(dev)[:0], 0, who)
+            return SimplifiedMesh(empty_v, empty_i.reshape(0, 3), empty_i, empty_i.clone(), out_a)
+        p = vf.to(dev).contiguous()
+        tt = t.to(dev, torch.int32).contiguous()
+        ws = _simplify_workspace(nv, nt, dims, dev)
+        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        _simplify_count(p, tt, o, cell, dims, ws, totals)
+        kv, kt = (int(x) for x in totals.cpu())  # (the second and last host read: the output sizes)
+        out_v = torch.empty((kv, 3), device=dev, dtype=torch.float32)
+        out_t = torch.empty((kt, 3), device=dev, dtype=torch.int32)
+        vertex_map = torch.empty(nv, device=dev, dtype=torch.int32)
+        reps = torch.empty(kv, device=dev, dtype=torch.int32)
+        _simplify_emit(p, tt, o, cell, dims, ws, out_v, out_t, vertex_map, reps)
+        idx = reps.long()
+        out_a = _gather_attrs(attrs, lambda a: torch.as_tensor(a).to(dev).index_select(0, idx), nv, who)
+    return SimplifiedMesh(out_v, out_t, vertex_map, reps, out_a)
+
+
+def simplify_mesh_reference(vertices, triangles, cell, attrs=None, origin=None):
+    """NumPy implementation of `simplify_mesh`'s contract (module docstring): its checker, with the same argument
+    errors.  Returns SimplifiedMesh of arrays (attrs gathered on the host)."""
+    who = "simplify_mesh_reference"
+    host = _lib.host_array
+    p = np.ascontiguousarray(host(vertices), dtype=_F)
+    tri = np.asarray(host(triangles))
+    cell, origin = _simplify_args(p.shape, tri, cell, origin, attrs, who)
+    tri = np.ascontiguousarray(tri, dtype=np.int64)
+    nv, nt = len(p), len(tri)
+    if nv == 0:
+        _simplify_grid(np.zeros(3, _F), np.zeros(3, _F), True, tri.min() if nt else None, tri.max() if nt else None,
+                       0, cell, origin, who)
+        none = np.zeros(0, np.int32)
+        return SimplifiedMesh(np.zeros((0, 3), _F), none.reshape(0, 3), none, none.copy(),
+                              _gather_attrs(attrs, lambda a: host(a)[:0], 0, who))
+    with np.errstate(all="ignore"):
+        finite = bool(np.isfinite(p).all())
+        o, dims = _simplify_grid(p.min(0), p.max(0), finite, tri.min() if nt else None, tri.max() if nt else None, nv,
+                                 cell, origin, who)
+        q = (p - o) / cell
+        c = np.floor(q)
+        valid = np.isfinite(q).all(1) & (c >= 0).all(1) & (c < dims.astype(_F)).all(1)
+    members = np.nonzero(valid)[0]  # ascending: the first member of a cell in this order is its smallest id
+    ci = c[members].astype(np.int64)
+    keys = (ci[:, 0] * int(dims[1]) + ci[:, 1]) * int(dims[2]) + ci[:, 2]
+    _, first, cell_of_member = np.unique(keys, return_index=True, return_inverse=True)
+    reps = np.sort(members[first])
+    new_of_cell = np.empty(len(first), np.int64)
+    new_of_cell[np.argsort(members[first], kind="stable")] = np.arange(len(first))
+    vertex_map = np.full(nv, -1, np.int64)
+    vertex_map[members] = new_of_cell[cell_of_member.reshape(-1)]
+    # the fixed-point mean
+    r = (q - c)[members]
+    assert np.array_equal(r.astype(np.float64), q[members].astype(np.float64) - c[members].astype(np.float64)), \
+        "q - floor(q) is exact in fp32"
+    fixed = np.rint(r * _F(2.0 ** 20)).astype(np.int64)
+    sums = np.zeros((len(reps), 3), np.int64)
+    np.add.at(sums, vertex_map[members], fixed)
+    count = np.bincount(vertex_map[members], minlength=len(reps))
+    m = (sums.astype(np.float64) / count.astype(np.float64)[:, None] * 2.0 ** -20).astype(_F)
+    out_v = (o + cell * (c[reps] + m)).astype(_F)  # (float32 operands throughout: each operation rounds to float32)
+    # the triangles
+    mapped = vertex_map[tri]
+    live = (mapped >= 0).all(1) & (mapped[:, 0] != mapped[:, 1]) & (mapped[:, 1] != mapped[:, 2]) & \
+        (mapped[:, 0] != mapped[:, 2])
+    alive = np.nonzero(live)[0]
+    if len(alive):
+        sets = np.sort(mapped[alive], axis=1)
+        nk = max(len(reps), 1)
+        if nk ** 3 < 2 ** 62:
+            _, firsts = np.unique((sets[:, 0] * nk + sets[:, 1]) * nk + sets[:, 2], return_index=True)
+        else:
+            _, firsts = np.unique(sets, axis=0, return_index=True)
+        alive = np.sort(alive[firsts])  # (return_index: the first occurrence, the smallest original index)
+    out_t = mapped[alive].astype(np.int32).reshape(-1, 3)
+    out_a = _gather_attrs(attrs, lambda a: host(a)[reps], nv, who)
+    return SimplifiedMesh(out_v, out_t, vertex_map.astype(np.int32), reps.astype(np.int32), out_a)

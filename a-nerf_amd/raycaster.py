@@ -214,7 +214,7 @@ class RayCaster:
     @torch.no_grad()
     def extract_mesh(self, kps, skts, bones, radius=1.8, res=255, threshold=10., network=None, coords="unit",
                      flip=False, normals=False, colors=False, view="normal", cams=None, keep_largest=None,
-                     min_triangles=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                     min_triangles=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, simplify=None):
         """run_render.render_mesh's body for one pose (run_render.py:980-985) without leaving the device: the
         render_mesh_density grid, clamped at 0, and its iso-surface at `threshold` (isosurface.py).  Returns
         (vertices float32 [V, 3], triangles int32 [T, 3]) device tensors; `coords`: "unit" (vertices / res - .5,
@@ -230,7 +230,11 @@ class RayCaster:
         mu=smooth_mu, open edges pinned) before the coordinate mapping and the colour query: the voxel staircases
         and ripple go, the volume stays.  attrs["normals"] remain the gradient normals of the unsmoothed crossing,
         unless normals="faces": then they are the face-accumulated normals of the final vertices
-        (meshops.vertex_normals, the colouring of the reference's viewer), which also direct view="normal"."""
+        (meshops.vertex_normals, the colouring of the reference's viewer), which also direct view="normal".
+        `simplify`: a cell edge in voxels runs vertex clustering (meshops.simplify_mesh, cells aligned with the voxel
+        grid) after the filter and the smoothing and before the coordinate mapping and the colour query: fewer
+        vertices reach the network.  Gradient normals are those of each cell's first vertex; normals="faces" are
+        computed on the simplified mesh (isosurface.mesh_from_grid)."""
         from .isosurface import mesh_from_grid
         if colors and self._staged is not None:
             raise NotImplementedError("extract_mesh(colors=True): staged encoders (multires_bones > 0, relpos / "
@@ -243,7 +247,7 @@ class RayCaster:
         return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip, normals=normals,
                               colors=colors, view=view, cams=cams, radiance=radiance, keep_largest=keep_largest,
                               min_triangles=min_triangles, smooth=smooth, smooth_lambda=smooth_lambda,
-                              smooth_mu=smooth_mu)
+                              smooth_mu=smooth_mu, simplify=simplify)
 
     def render_rays(self, ray_batch, N_samples, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                     subject_idxs=None, retraw=False, lindisp=False, perturb=0., N_importance=0, network_fine=None,

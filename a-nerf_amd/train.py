@@ -920,7 +920,7 @@ class StagedCaster:
     @torch.no_grad()
     def extract_mesh(self, kps, skts, bones, radius=1.8, res=255, threshold=10., network=None, coords="unit",
                      flip=False, normals=False, colors=False, view="normal", cams=None, keep_largest=None,
-                     min_triangles=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+                     min_triangles=0, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53, simplify=None):
         """As RayCaster.extract_mesh, on this caster's own render_mesh_density grid (it stays on the device).
         Normals come from the grid and work here; colours need the fused network's point-wise radiance query."""
         from .isosurface import mesh_from_grid
@@ -930,7 +930,7 @@ class StagedCaster:
         grid = self.render_mesh_density(kps, skts, bones, radius=radius, res=res, network=network)
         return mesh_from_grid(grid, kps, radius, int(res), threshold, coords=coords, flip=flip, normals=normals,
                               keep_largest=keep_largest, min_triangles=min_triangles, smooth=smooth,
-                              smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
+                              smooth_lambda=smooth_lambda, smooth_mu=smooth_mu, simplify=simplify)
 
 
 def _img_loss(name, x, y, reduction="mean", beta=0.1):

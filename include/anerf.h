@@ -32,6 +32,8 @@
  *   anerf_mesh_smooth       the reference leaves smoothing to the user: trimesh.smoothing.filter_taubin on the host)
  *   anerf_mesh_vertex_normals   compute_normal of the reference's mesh viewer (face normals summed per vertex) and
  *   anerf_mesh_raster       what its OpenGL pass draws: an orthographic view of the mesh (ABI 24)   render_mesh.py:35-54, 164-182
+ *   anerf_mesh_simplify_*   vertex clustering of that mesh on a grid of cells (ABI 25; the reference leaves decimation
+ *                           to the user: trimesh with open3d or fast_simplification on the host)
  *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
  *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
@@ -75,7 +77,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 24
+#define ANERF_ABI_VERSION 25
 
 enum {
     ANERF_OK = 0,
@@ -528,6 +530,53 @@ int anerf_mesh_raster(const float* vertices, int64_t n_vertices, const int32_t* 
                       const float* transform, int32_t width, int32_t height, const float* attrs, int32_t n_channels,
                       const float* background, int32_t* face_ids, float* depth, float* bary, float* image, void* ws,
                       size_t ws_bytes, void* stream);
+
+/* ABI 25: vertex clustering (Rossignac-Borrel) of such a mesh: the vertices are snapped to a uniform grid of cells,
+ * every cell's vertices become one, and the triangles that collapse or become copies of one another are dropped.
+ * Inputs: vertices float [n_vertices][3], triangles int32 [n_tri][3] (device); origin o: HOST float [3]; cell > 0;
+ * dims n: HOST int32 [3], every n_a >= 1 and n_0 n_1 n_2 <= ANERF_SIMPLIFY_MAX_CELLS; all read during the call.
+ * fp32, every operation separately rounded, divisions correctly rounded:
+ *   cell      q_a = (p_a - o_a) / cell, c_a = floor(q_a); the vertex is VALID iff all three q_a are finite and
+ *             0 <= c_a < n_a; its key is (c_0 n_1 + c_1) n_2 + c_2;
+ *   merge     a cell's representative is its valid member with the smallest vertex id; the new vertices are the
+ *             representatives in ascending original id (the relative order is kept, as in anerf_mesh_compact_*):
+ *             vertex_map [n_vertices]   the new id of the vertex's cell, or -1 for a vertex that is not valid;
+ *             representatives [V']      the original id of new vertex j (the gather index of per-vertex arrays);
+ *   position  the fixed-point mean of the cell's members, which has no order: r_a = q_a - (float) c_a (exact),
+ *             i_a = (int64) rint(r_a 2^20); S_a = the 64-bit integer sum of i_a over the members, n their number;
+ *             m_a = (float) ((double) S_a / (double) n * 2^-20); p'_a = o_a + cell * ((float) c_a + m_a);
+ *   triangles (a, b, c) maps to (a', b', c') through vertex_map; it is dropped if an id is outside [0, n_vertices), a
+ *             mapped id is -1, two mapped ids are equal, or an earlier surviving triangle (a smaller index) has the
+ *             same unordered set {a', b', c'}, in either winding.  The survivors keep their relative order and their
+ *             own vertex order: neither rotated nor re-wound.
+ * Integers or a fixed order of roundings throughout: the same bits on every run and under any schedule.
+ * anerf_mesh_simplify_count writes totals_dev (device, int64 [2]: V', T') and leaves its decisions in ws; the caller
+ * reads the 16 bytes (the one synchronisation), allocates, and calls anerf_mesh_simplify_emit with the SAME inputs and
+ * ws and with n_out_v = V', n_out_t = T', the rows of out_vertices float [V'][3], representatives [V'] and
+ * out_triangles [T'][3] (an output may be NULL where its extent is 0).  The totals live on the device, so the host can
+ * refuse only sizes that no count can give (outside [0, n_vertices] / [0, n_tri]); with other sizes no store goes
+ * past the sizes given, rows beyond them are dropped.  A vertex that is not valid (a NaN or infinite coordinate among
+ * them) and a triangle with an id outside [0, n_vertices) are dropped and never dereferenced.  Representatives by an
+ * integer atomic min per vertex into a table over the cells, the sums by 64-bit integer atomic adds; duplicate sets
+ * through per-owner rows (the owner: the triangle's smallest representative): a row of up to 32 entries is searched by
+ * its triangles' own threads, a longer one sorted by a workgroup's bitonic network; no kernel waits for another
+ * workgroup.  n_vertices == 0 and n_tri == 0 are valid (vertices and triangles may be NULL where their extent is 0).
+ * ws: anerf_mesh_simplify_workspace(n_vertices, n_tri, n_cells = n_0 n_1 n_2) bytes, 8-byte aligned (never 0 for valid
+ * arguments; 0, with a message, for counts outside [0, 2^31) or n_cells outside [1, 2^26]).  Allocation-free,
+ * asynchronous on `stream`.  ANERF_EINVAL, before any HIP call, for such counts, a NULL pointer with a non-zero extent,
+ * a NULL origin, dims or totals, a cell that is not finite and > 0, an origin that is not finite, a dims entry below 1
+ * or a dims product outside [1, 2^26], a NULL, misaligned or short workspace, output sizes outside the ranges above.
+ * Out of scope: quadric-error placement, edge-collapse decimation, target triangle counts, keeping the result
+ * manifold (clustering can pinch thin parts into edges with more than two triangles). */
+#define ANERF_SIMPLIFY_MAX_CELLS (1 << 26)
+size_t anerf_mesh_simplify_workspace(int64_t n_vertices, int64_t n_tri, int64_t n_cells);
+int anerf_mesh_simplify_count(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                              const float* origin, float cell, const int32_t* dims, void* ws, size_t ws_bytes,
+                              int64_t* totals_dev, void* stream);
+int anerf_mesh_simplify_emit(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                             const float* origin, float cell, const int32_t* dims, const void* ws, size_t ws_bytes,
+                             float* out_vertices, int64_t n_out_v, int32_t* out_triangles, int64_t n_out_t,
+                             int32_t* vertex_map, int32_t* representatives, void* stream);
 
 /* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
  * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /

@@ -1,0 +1,132 @@
+"""Meshes and expected results shared by test_mesh_simplify.py (CPU) and test_gpu_mesh_simplify.py, on top of _mesh_cases
+and _smooth_cases.  Everything is computed once per session and handed out read-only."""
+import functools
+import importlib
+
+import numpy as np
+
+import _mesh_cases as M
+import _smooth_cases as S
+
+meshops = importlib.import_module("a-nerf_amd.meshops")
+
+F = np.float32
+CELLS = (0.5, 1.0, 2.0, 3.7)
+NAMED = ("sphere", "torus", "two_spheres", "blobs", "random33")
+FIELDS = ("vertices", "triangles", "vertex_map", "representatives")
+
+
+def _ro(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def mesh(case):
+    """(vertices, triangles) of a named mesh, or of "name/kind": the same mesh with vertex v renamed
+    permutation(V, kind)[v] (its position moves with it)."""
+    if "/" not in case:
+        return M.mesh(case)
+    name, kind = case.split("/")
+    v, t = M.mesh(name)
+    perm = M.permutation(len(v), kind)
+    moved = np.empty_like(v)
+    moved[perm] = v
+    return _ro(moved, M.relabel(t, perm))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case, cell, origin=None):
+    """simplify_mesh_reference of a case (read-only arrays)."""
+    v, t = mesh(case)
+    ref = meshops.simplify_mesh_reference(v, t, cell, origin=origin)
+    _ro(*ref[:4])
+    return ref
+
+
+def brute_force(vertices, triangles, cell, origin=None):
+    """The contract again with dicts and loops, one vertex and one triangle at a time, in float32 scalars:
+    (vertices, triangles, vertex_map, representatives).  Every vertex is taken to lie in the grid."""
+    p = np.asarray(vertices, F)
+    cell = F(cell)
+    o = p.min(0) if origin is None else np.asarray(origin, F)
+    members, q_of = {}, []
+    for i in range(len(p)):
+        q = [(p[i, a] - o[a]) / cell for a in range(3)]
+        assert all(type(x) is F for x in q)
+        members.setdefault(tuple(int(np.floor(x)) for x in q), []).append(i)  # (ascending: the first is the smallest)
+        q_of.append(q)
+    reps = sorted(m[0] for m in members.values())
+    new_id = {r: j for j, r in enumerate(reps)}
+    vertex_map = [-1] * len(p)
+    out_v = np.zeros((len(reps), 3), F)
+    for c, m in members.items():
+        j = new_id[m[0]]
+        for i in m:
+            vertex_map[i] = j
+        for a in range(3):
+            total = sum(int(np.rint((q_of[i][a] - F(c[a])) * F(2.0 ** 20))) for i in m)  # Python integers
+            mean = F(total / len(m) * 2.0 ** -20)  # (int / int: correctly rounded to a double)
+            out_v[j, a] = o[a] + cell * (F(c[a]) + mean)
+    seen, out_t = set(), []
+    for a, b, c in np.asarray(triangles).reshape(-1, 3).tolist():
+        mapped = (vertex_map[a], vertex_map[b], vertex_map[c])
+        if len(set(mapped)) < 3 or frozenset(mapped) in seen:
+            continue
+        seen.add(frozenset(mapped))
+        out_t.append(mapped)
+    return (out_v, np.asarray(out_t, np.int32).reshape(-1, 3), np.asarray(vertex_map, np.int32),
+            np.asarray(reps, np.int32))
+
+
+def dropped(case, cell):
+    """(collapsed, duplicates): the triangles of a case dropped by either rule, counted from the checker's
+    vertex_map alone."""
+    _, t = mesh(case)
+    ref = reference(case, cell)
+    mapped = ref.vertex_map[t]
+    collapsed = int(((mapped[:, 0] == mapped[:, 1]) | (mapped[:, 1] == mapped[:, 2]) |
+                     (mapped[:, 0] == mapped[:, 2])).sum())
+    return collapsed, len(t) - collapsed - len(ref.triangles)
+
+
+def edge_counts(tri):
+    """The number of triangles on every undirected edge of the list."""
+    e = np.sort(np.concatenate([tri[:, [0, 1]], tri[:, [1, 2]], tri[:, [2, 0]]]).astype(np.int64), axis=1)
+    return np.unique(e, axis=0, return_counts=True)[1]
+
+
+def euler(tri):
+    """V - E + F of the surface the triangles make, V the vertices they use: a cell whose triangles all collapse
+    leaves a vertex that no triangle uses (three of the sphere's 29 at cell 3.7), which is no part of the surface."""
+    return len(np.unique(tri)) - len(edge_counts(tri)) + len(tri)
+
+
+# ------------------------------------------------------------------ lists whose answer is known by construction
+@functools.lru_cache(maxsize=None)
+def strip(nv):
+    """(vertices, triangles) of _mesh_cases' strip over nv vertices, vertex i at (0.25 i, i % 2, 0): with cell 1 from
+    the origin every cell holds two vertices (i and i + 2) and about half the triangles survive."""
+    i = np.arange(nv)
+    v = np.stack([0.25 * i, (i % 2).astype(np.float64), np.zeros(nv)], 1).astype(F)
+    return _ro(v)[0], M.strip_triangles(nv)
+
+
+@functools.lru_cache(maxsize=None)
+def wheel(n, period=None):
+    """(vertices, triangles) of _smooth_cases' wheel: the hub at (0.5, 0.5, 0.5), rim vertex i at (1.5 + i, 0.5, 0.5),
+    or at (1.5 + i % period, 0.5, 0.5).  With cell 1 from the origin nothing merges without a period: the hub owns
+    all n triangles.  With period 7 the rim falls into 7 cells."""
+    tri, nv = S.wheel(n)
+    i = np.arange(n)
+    x = 1.5 + (i if period is None else i % period)
+    v = np.concatenate([[[0.5, 0.5, 0.5]], np.stack([x, np.full(n, 0.5), np.full(n, 0.5)], 1)]).astype(F)
+    assert len(v) == nv
+    return _ro(v)[0], tri
+
+
+def small(name, seed=3):
+    """(vertices, triangles) of one of _mesh_cases' small synthetic lists, at fixed random positions."""
+    tri, nv, _ = M.synthetic(name)
+    return np.random.default_rng(seed).uniform(-2, 2, (nv, 3)).astype(F), tri

@@ -10,5 +10,5 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fP
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-mfma-vgpr-form -c -o tools/ab/stamps_render_f16.o $C/anerf_render_f16.hip
 wait %1
 /opt/rocm/bin/hipcc $F -shared -o tools/ab/libanerf_hip_stamps.so tools/ab/stamps_render.o tools/ab/stamps_render_f16.o \
-    $C/anerf_gemm.hip $C/anerf_iso.hip $C/anerf_mesh.hip $C/anerf_raster.hip
+    $C/anerf_gemm.hip $C/anerf_iso.hip $C/anerf_mesh.hip $C/anerf_raster.hip $C/anerf_simplify.hip
 rm -f tools/ab/stamps_render.o tools/ab/stamps_render_f16.o

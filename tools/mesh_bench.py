@@ -34,6 +34,15 @@ turntable_ms, mesh_turntable at its defaults (91 frames of 512 x 512, normals in
 rasterize_mesh_reference (NumPy) on the body's frame, once, for scale; the device frame is checked against it bit for
 bit.
 
+Simplification (meshops.simplify_mesh; csrc/anerf_simplify.hip), on the same filtered body in index coordinates from
+the origin (0, 0, 0), as extract_mesh(simplify=) runs it, at cell = 2 voxels and (the simplify4_* keys) cell = 4:
+simplify_ms, simplify_mesh whole (the bounding box and id range read, the kernels, the host read of the totals);
+simplify_kernels_ms, anerf_mesh_simplify_count and _emit back to back into preallocated outputs, no host read between
+them; simplify_vertices / simplify_triangles, what is left; extract_mesh_simplify_ms, extract_mesh(keep_largest=1,
+smooth=10, simplify=2.0, colors=True), next to extract_mesh_smooth_colors_ms, the same call without simplify;
+simplify_reference_host_ms, simplify_mesh_reference (NumPy) at cell 2, once, for scale; the device results are checked
+against the checker bit for bit.
+
 Prints one JSON line, and appends it to the file given with --append (the record: profiles/mesh_bench.jsonl).
 Usage: python tools/mesh_bench.py [res] [precision] [--append FILE]"""
 import importlib
@@ -188,6 +197,47 @@ def _raster_legs(v, t):
             "raster_reference_host_ms": round(ref_ms, 1)}
 
 
+def _simplify_legs(rc, kps, skts, res, thr, v, t):
+    """Vertex clustering of the body (the mesh keep_largest=1 leaves), in index coordinates from the origin."""
+    v, t = meshops.filter_mesh(v, t, keep_largest=1)
+    nv = int(v.shape[0])
+    v_host, t_host = v.cpu().numpy(), t.cpu().numpy()
+    origin = (0.0, 0.0, 0.0)
+    out = {}
+    for cell, key in ((2.0, "simplify"), (4.0, "simplify4")):
+        whole_ms, got = _time(lambda: meshops.simplify_mesh(v, t, cell, origin=origin), reps=20)
+        kv, kt = int(got.vertices.shape[0]), int(got.triangles.shape[0])
+        c32 = np.float32(cell)
+        o = np.zeros(3, np.float32)
+        dims = (np.floor(v.amax(0).cpu().numpy() / c32).astype(np.int32) + 1)
+        ws = meshops._simplify_workspace(nv, int(t.shape[0]), dims, v.device)
+        totals = torch.empty(2, device=v.device, dtype=torch.int64)
+        out_v, out_t = torch.empty_like(got.vertices), torch.empty_like(got.triangles)
+        vmap, reps = torch.empty_like(got.vertex_map), torch.empty_like(got.representatives)
+
+        def kernels():  # both entries back to back, no host read
+            meshops._simplify_count(v, t, o, c32, dims, ws, totals)
+            meshops._simplify_emit(v, t, o, c32, dims, ws, out_v, out_t, vmap, reps)
+        kernels_ms, _ = _time(kernels, reps=20)
+        assert totals.tolist() == [kv, kt]
+        t0 = time.perf_counter()
+        ref = meshops.simplify_mesh_reference(v_host, t_host, cell, origin=origin)
+        ref_ms = (time.perf_counter() - t0) * 1e3
+        for mine in (got, (out_v, out_t, vmap, reps)):
+            for g, r in zip(mine, ref[:4]):
+                g = g.cpu().numpy()
+                assert g.shape == r.shape and np.array_equal(g.view(np.int32), r.view(np.int32))
+        out.update({key + "_ms": round(whole_ms, 3), key + "_kernels_ms": round(kernels_ms, 3),
+                    key + "_vertices": kv, key + "_triangles": kt})
+        if cell == 2.0:
+            out["simplify_reference_host_ms"] = round(ref_ms, 1)
+    kw = dict(radius=1.8, res=res, threshold=thr, keep_largest=1, smooth=10, colors=True)
+    plain_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, **kw))
+    simple_ms, _ = _time(lambda: rc.extract_mesh(kps, skts, None, simplify=2.0, **kw))
+    out.update({"extract_mesh_smooth_colors_ms": round(plain_ms, 3), "extract_mesh_simplify_ms": round(simple_ms, 3)})
+    return out
+
+
 def main():
     argv = list(sys.argv[1:])
     append = None
@@ -216,6 +266,7 @@ def main():
     legs = _filter_legs(rc, kps, skts, res, thr, v, ti, ni)
     legs.update(_smooth_legs(rc, kps, skts, res, thr, v, ti))
     legs.update(_raster_legs(v, ti))
+    legs.update(_simplify_legs(rc, kps, skts, res, thr, v, ti))
     n = (res + 1) ** 3
     line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
                       "grid_ms": round(grid_ms, 3), "isosurface_ms": round(iso_ms, 3),
