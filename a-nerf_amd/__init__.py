@@ -12,7 +12,9 @@ from .isosurface import isosurface, isosurface_reference, mesh_from_grid, read_p
 from .meshops import (filter_mesh, mesh_components, mesh_components_reference, mesh_turntable, rasterize_mesh,
                       rasterize_mesh_reference, simplify_mesh, simplify_mesh_reference, smooth_mesh,
                       smooth_mesh_reference, turntable_transforms, vertex_adjacency, vertex_adjacency_reference,
-                      vertex_normals, vertex_normals_reference, SimplifiedMesh, SIMPLIFY_MAX_CELLS)
+                      vertex_normals, vertex_normals_reference, SimplifiedMesh, SIMPLIFY_MAX_CELLS, camera_view,
+                      rasterize_mesh_camera, rasterize_mesh_camera_reference, render_mesh_views,
+                      render_mesh_views_reference, MeshRaster, MeshViews)
 from . import dataset, rays, synthetic, train
 from .dataset import RayImageDataset, RayImageSampler
 
@@ -23,4 +25,5 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "vertex_adjacency_reference", "smooth_mesh", "smooth_mesh_reference", "vertex_normals",
            "vertex_normals_reference", "rasterize_mesh", "rasterize_mesh_reference", "mesh_turntable",
            "turntable_transforms", "simplify_mesh", "simplify_mesh_reference", "SimplifiedMesh",
-           "SIMPLIFY_MAX_CELLS"]
+           "SIMPLIFY_MAX_CELLS", "camera_view", "rasterize_mesh_camera", "rasterize_mesh_camera_reference",
+           "render_mesh_views", "render_mesh_views_reference", "MeshRaster", "MeshViews"]

@@ -39,7 +39,7 @@ ANERF_ENC_VIEW_WINDOWS = 128  # training layout: the view part as the NJ view wi
 ANERF_SMOOTH_TAUBIN = 1  # anerf_mesh_smooth's flags: a step with mu after every step with lambda
 ANERF_RASTER_SMALL_PIXELS = 256  # include/anerf.h: the clipped bounding box up to which a triangle's own thread draws it
 ANERF_SIMPLIFY_MAX_CELLS = 1 << 26  # include/anerf.h: the cells anerf_mesh_simplify_*'s table may have
-ABI_VERSION = 25  # include/anerf.h ANERF_ABI_VERSION: the structs below
+ABI_VERSION = 26  # include/anerf.h ANERF_ABI_VERSION: the structs below
 
 
 class ModelDesc(ctypes.Structure):
@@ -186,6 +186,13 @@ SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
+    "anerf_mesh_raster_persp_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                            ctypes.c_int32]),
+    "anerf_mesh_raster_persp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "anerf_mesh_simplify_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "anerf_mesh_simplify_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                  ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,

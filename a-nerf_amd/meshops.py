@@ -39,8 +39,14 @@ by normals).  `vertex_normals` (anerf_mesh_vertex_normals), `rasterize_mesh` (an
 do it on the device, csrc/anerf_raster.hip; their contract, shared with `vertex_normals_reference` /
 `rasterize_mesh_reference` (NumPy checkers, reached only by those names), is written out in include/anerf.h and
 DESIGN.md: quantised face normals summed as 64-bit integers; coverage on vertices snapped to 1 / 256 pixel with
-integer edge functions and a tie rule; a depth test that is one 64-bit atomic min per fragment.  Orthographic / affine
-cameras only: no perspective, no near-plane clipping, no multisampling, and no image files are written.
+integer edge functions and a tie rule; a depth test that is one 64-bit atomic min per fragment.  Those are the viewer's
+orthographic / affine cameras.  `camera_view`, `rasterize_mesh_camera` (anerf_mesh_raster_persp) and
+`render_mesh_views` draw the mesh through the perspective cameras everything else here speaks in (c2w, H, W, focal,
+center: render_path, gen_rays, the dataset), checked by `rasterize_mesh_camera_reference`: triangles are cut at the
+near plane (a cut point is a function of its edge's IN and OUT end alone, so neighbours get the same bits: no cracks),
+the cut polygon is fanned into one or two sub-triangles that go through the same integer coverage, 1 / depth is
+interpolated (perspective-correct depth, weights and attributes), and the key holds the camera depth and the original
+triangle's id.  No side-plane clipping, no multisampling, no back-face culling, and no image files are written.
 
 The extracted mesh is as dense as the grid (two triangles per surface voxel), and whoever takes it further decimates it
 first; the reference leaves that to trimesh, which needs open3d or fast_simplification for it.  `simplify_mesh` is
@@ -611,7 +617,7 @@ def rasterize_mesh(vertices, triangles, transform, width, height, attrs=None, ba
     `rasterize_mesh_reference`.  Triangles whose clipped bounding box holds more than RASTER_SMALL_PIXELS pixel
     centres are drawn by whole workgroups, smaller ones by one thread each: the same bits either way.
     ValueError before anything is launched: ids outside [0, V), width or height outside [1, 16384], attrs rows != V.
-    Four launches on the current stream, no host read.  Out of scope: perspective cameras and near-plane clipping,
+    Four launches on the current stream, no host read.  Perspective cameras: `rasterize_mesh_camera`.  Out of scope:
     multisampling, writing image files."""
     shape = tuple(vertices.shape) if hasattr(vertices, "shape") else np.shape(vertices)
     ashape = None if attrs is None else (tuple(attrs.shape) if hasattr(attrs, "shape") else np.shape(attrs))
@@ -628,8 +634,36 @@ _RASTER_CHUNK = 1 << 21  # candidate fragments per pass of the checker
 _EMPTY_KEY = np.uint64(0xffffffffffffffff)
 
 
-def _fragments_reference(X, Y, z, a2, flip, tid, i, j):
-    """The contract's fragment of triangles `tid` at pixels (i, j) (arrays of one length): (ok, b0, b1, b2, z)."""
+def _boxes_reference(X, Y, W, H):
+    """Of triangles snapped to X, Y (int64 [T, 3]): twice the area made positive, whether it was negative, and the
+    pixel columns i0 .. i1 and rows j0 .. j1 whose centres the bounding box holds, clipped to the image."""
+    a2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
+    i0 = np.maximum((X.min(1) - 128 + 255) >> 8, 0)
+    i1 = np.minimum((X.max(1) - 128) >> 8, W - 1)
+    j0 = np.maximum((Y.min(1) - 128 + 255) >> 8, 0)
+    j1 = np.minimum((Y.max(1) - 128) >> 8, H - 1)
+    return np.abs(a2), a2 < 0, i0, i1, j0, j1
+
+
+def _candidates_reference(live, i0, i1, j0, j1):
+    """The candidate fragments (triangle, column, row) of the triangles `live` over their boxes, a bounded number at
+    a time (a larger box: a pass of its own)."""
+    bw = (i1 - i0 + 1)[live]
+    box = bw * (j1 - j0 + 1)[live]
+    start = 0
+    while start < len(live):
+        end = start + max(1, int(np.searchsorted(np.cumsum(box[start:]), _RASTER_CHUNK, side="right")))
+        sel, n = live[start:end], box[start:end]
+        tid = np.repeat(sel, n)
+        k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+        w = np.repeat(bw[start:end], n)
+        yield tid, i0[tid] + k % w, j0[tid] + k // w
+        start = end
+
+
+def _coverage_reference(X, Y, a2, flip, tid, i, j):
+    """The contract's coverage of triangles `tid` at pixels (i, j) (arrays of one length), shared by the affine and
+    the perspective checker: (inside, b0, b1, b2)."""
     px, py = 256 * i + 128, 256 * j + 128
     inside = np.ones(len(tid), bool)
     E = {}
@@ -645,6 +679,13 @@ def _fragments_reference(X, Y, z, a2, flip, tid, i, j):
         b1 = E[(2, 0)].astype(_F) / area
         b2 = E[(0, 1)].astype(_F) / area
         b0 = (_F(1) - b1) - b2
+    return inside, b0, b1, b2
+
+
+def _fragments_reference(X, Y, z, a2, flip, tid, i, j):
+    """The contract's fragment of triangles `tid` at pixels (i, j) (arrays of one length): (ok, b0, b1, b2, z)."""
+    inside, b0, b1, b2 = _coverage_reference(X, Y, a2, flip, tid, i, j)
+    with np.errstate(all="ignore"):
         zz = (b0 * z[tid, 0] + b1 * z[tid, 1]) + b2 * z[tid, 2]
         ok = inside & (zz >= 0) & (zz <= 1)
     zz = np.where(zz == 0, _F(0), zz).astype(_F)
@@ -671,29 +712,12 @@ def rasterize_mesh_reference(vertices, triangles, transform, width, height, attr
             X = np.rint(s[..., 0] * _F(256)).astype(np.int64)
             Y = np.rint(s[..., 1] * _F(256)).astype(np.int64)
         z = np.ascontiguousarray(s[..., 2])
-        a2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
-        flip = a2 < 0
-        a2 = np.abs(a2)
-        i0 = np.maximum((X.min(1) - 128 + 255) >> 8, 0)
-        i1 = np.minimum((X.max(1) - 128) >> 8, W - 1)
-        j0 = np.maximum((Y.min(1) - 128 + 255) >> 8, 0)
-        j1 = np.minimum((Y.max(1) - 128) >> 8, H - 1)
+        a2, flip, i0, i1, j0, j1 = _boxes_reference(X, Y, W, H)
         live = np.nonzero(good & (a2 != 0) & (i0 <= i1) & (j0 <= j1))[0]
-        bw = (i1 - i0 + 1)[live]
-        box = bw * (j1 - j0 + 1)[live]
-        # candidates (triangle, pixel of its box), a bounded number at a time (a larger box: a pass of its own)
-        start = 0
-        while start < len(live):
-            end = start + max(1, int(np.searchsorted(np.cumsum(box[start:]), _RASTER_CHUNK, side="right")))
-            sel, n = live[start:end], box[start:end]
-            tid = np.repeat(sel, n)
-            k = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
-            w = np.repeat(bw[start:end], n)
-            i, j = i0[tid] + k % w, j0[tid] + k // w
+        for tid, i, j in _candidates_reference(live, i0, i1, j0, j1):
             ok, _, _, _, zz = _fragments_reference(X, Y, z, a2, flip, tid, i, j)
             key = (zz[ok].view(np.uint32).astype(np.uint64) << np.uint64(32)) | tid[ok].astype(np.uint64)
             np.minimum.at(keys, (j[ok] * W + i[ok]), key)
-            start = end
     hit = np.nonzero(keys != _EMPTY_KEY)[0]
     face_ids = np.full(H * W, -1, np.int32)
     depth = np.full(H * W, np.inf, _F)
@@ -778,6 +802,10 @@ def _to_uint8_reference(image):
     return x.astype(np.uint8)
 
 
+def _to_uint8(image):
+    return torch.round(torch.nan_to_num(image, nan=0.0).clamp_(0.0, 1.0).mul_(255.0)).to(torch.uint8)
+
+
 def _turntable_colors(colors, n_vertices, who, normals):
     """The per-vertex colours float32 [V, 3] in [0, 1]: given (uint8: c * fl(1 / 255)), or 0.5 n + 0.5 of normals()."""
     if colors is None:
@@ -820,7 +848,7 @@ def mesh_turntable(vertices, triangles, colors=None, frames=91, step_deg=4.0, wi
         out = torch.empty((len(Ts), height, width, 3), device=dev, dtype=torch.uint8)
         for k in range(len(Ts)):
             img = _raster_launch(p, t, np.ascontiguousarray(Ts[k]), width, height, c, nch, bg, ws).image
-            out[k] = torch.round(torch.nan_to_num(img, nan=0.0).clamp_(0.0, 1.0).mul_(255.0)).to(torch.uint8)
+            out[k] = _to_uint8(img)
     return out
 
 
@@ -837,6 +865,349 @@ def mesh_turntable_reference(vertices, triangles, colors=None, frames=91, step_d
     for k in range(len(Ts)):
         out[k] = _to_uint8_reference(rasterize_mesh_reference(p, triangles, Ts[k], width, height, c, background).image)
     return out
+
+
+# ------------------------------------------------------------------ the dataset's perspective cameras
+def _focal_pair(focal, who):
+    f = np.asarray(focal, dtype=np.float64).reshape(-1)  # (a scalar or a pair, as rays._intrinsic takes it)
+    if f.size not in (1, 2):
+        raise ValueError(f"{who}: focal must be one value or (fx, fy), got {f.size} values")
+    return float(f[0]), float(f[-1])
+
+
+def camera_view(c2w, H, W, focal, center=None):
+    """(view float32 [3, 4], intrinsics float32 [4] = fx, fy, cx, cy), host arrays, of the camera that `render_path`,
+    `gen_rays` and the dataset describe by `c2w` (camera to world, [3, 4] or [4, 4]: x right, y up, looking along
+    -z), `H, W, focal` (one value or (fx, fy)) and `center` (the principal point's offsets (x, y); None: W / 2,
+    H / 2), for `rasterize_mesh_camera`.  In float64, cast at the end: with R = c2w[:3, :3] the rows of view are
+    R[:, 0], -R[:, 1], -R[:, 2] (right, down the image, along the optical axis), its translation -rows @ c2w[:3, 3];
+    cx = offset_x + 0.5, cy = offset_y + 0.5.  The centre of pixel (row j, column i), at (i + 0.5, j + 0.5), is then
+    the ray that get_rays / anerf_gen_rays cast for that pixel, dirs = ((i - offset_x) / fx, -(j - offset_y) / fy, -1),
+    and because that direction has unit depth the ray's parameter at the surface is the raster's depth[j, i]."""
+    c = np.asarray(_lib.host_array(c2w), dtype=np.float64)
+    if c.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"camera_view: c2w must be [3, 4] or [4, 4], got shape {c.shape}")
+    fx, fy = _focal_pair(focal, "camera_view")
+    if center is None:
+        ox, oy = 0.5 * float(W), 0.5 * float(H)
+    else:
+        o = np.asarray(_lib.host_array(center), dtype=np.float64).reshape(-1)
+        if o.size != 2:
+            raise ValueError(f"camera_view: center must be (x, y), got {o.size} values")
+        ox, oy = float(o[0]), float(o[1])
+    R = c[:3, :3]
+    rows = np.stack([R[:, 0], -R[:, 1], -R[:, 2]])
+    view = np.concatenate([rows, (-rows @ c[:3, 3])[:, None]], 1)
+    return np.ascontiguousarray(view, dtype=_F), np.array([fx, fy, ox + 0.5, oy + 0.5], dtype=_F)
+
+
+def _camera_range(box, c2w, near, far, who):
+    """(near, far) as float32 values: those given, or from the vertices' bounding box `box` = (min, max) in float64 --
+    D the camera's distance to the box's centre, rho its half-diagonal (1 for a box without extent):
+    near = max(D - rho, 1e-3 rho), far = D + rho."""
+    if near is None or far is None:
+        lo, hi = box
+        eye = np.asarray(_lib.host_array(c2w), dtype=np.float64)[:3, 3]
+        rho = 0.5 * float(np.linalg.norm(hi - lo))
+        rho = rho if rho > 0 else 1.0
+        D = float(np.linalg.norm(eye - 0.5 * (lo + hi)))
+        near = max(D - rho, 1e-3 * rho) if near is None else near
+        far = D + rho if far is None else far
+    near, far = _F(near), _F(far)
+    if not (np.isfinite(near) and near > 0):
+        raise ValueError(f"{who}: near must be finite and > 0, got {near}")
+    if not (np.isfinite(far) and far >= near):
+        raise ValueError(f"{who}: far must be finite and >= near ({near}), got {far}")
+    return near, far
+
+
+def _persp_args(vertices_shape, view, intrinsics, width, height, attrs_shape, background, who):
+    """The argument errors of the perspective rasteriser and its checker: (view float32 [3, 4], intrinsics float32
+    [4], C, background float32 [C])."""
+    _, nch, bg = _raster_args(vertices_shape, np.zeros((3, 4), _F), width, height, attrs_shape, background, who)
+    V = np.ascontiguousarray(_lib.host_array(view), dtype=_F)
+    K = np.ascontiguousarray(_lib.host_array(intrinsics), dtype=_F).reshape(-1)
+    if V.shape != (3, 4):
+        raise ValueError(f"{who}: view must be [3, 4], got shape {V.shape}")
+    if K.shape != (4,) or not np.isfinite(K).all() or K[0] == 0 or K[1] == 0:
+        raise ValueError(f"{who}: intrinsics must be finite (fx, fy, cx, cy) with fx, fy != 0, got {K}")
+    return V, K, nch, bg
+
+
+def _raster_persp_launch(p, t, V, K, near, far, width, height, a, nch, bg, ws):
+    """One anerf_mesh_raster_persp call on checked device tensors (ws: its workspace, reusable between frames)."""
+    dev = t.device
+    lib = _lib.load()
+    face_ids = torch.empty((height, width), device=dev, dtype=torch.int32)
+    depth = torch.empty((height, width), device=dev, dtype=torch.float32)
+    bary = torch.empty((height, width, 3), device=dev, dtype=torch.float32)
+    image = torch.empty((height, width, nch), device=dev, dtype=torch.float32) if nch else None
+    _lib.check(lib.anerf_mesh_raster_persp(_lib.ptr(p), int(p.shape[0]), _lib.ptr(t), int(t.shape[0]),
+                                           V.ctypes.data_as(ctypes.c_void_p), K.ctypes.data_as(ctypes.c_void_p),
+                                           float(near), float(far), width, height, _lib.ptr(a), nch,
+                                           bg.ctypes.data_as(ctypes.c_void_p) if nch else None, _lib.ptr(face_ids),
+                                           _lib.ptr(depth), _lib.ptr(bary), _lib.ptr(image), _lib.ptr(ws),
+                                           int(ws.shape[0]), _lib.stream_handle(dev)), "anerf_mesh_raster_persp")
+    return MeshRaster(face_ids, depth, bary, image)
+
+
+def _shape(x):
+    return None if x is None else (tuple(x.shape) if hasattr(x, "shape") else np.shape(x))
+
+
+@torch.no_grad()
+def rasterize_mesh_camera(vertices, triangles, c2w, H, W, focal, center=None, near=None, far=None, attrs=None,
+                          background=1.0):
+    """One view of a mesh (vertices float [V, 3], triangles int [T, 3]) on the device through the perspective camera
+    `c2w, H, W, focal, center` of `camera_view` -- the camera of render_path, gen_rays and the dataset, so the mesh is
+    drawn where the field is rendered.  Returns MeshRaster of device tensors, as `rasterize_mesh` does, with
+      face_ids  the ORIGINAL triangle's id (a triangle cut by the near plane keeps it);
+      depth     the camera depth of the surface at the pixel's centre: the parameter of that pixel's get_rays ray, to
+                set against the depth of render_rays; +inf where empty;
+      bary      perspective-correct weights over the triangle's three original vertices;
+      image     `attrs` under them.
+    Only depths in [near, far] are drawn: a triangle across the near plane is cut there (neighbours get the same cut
+    points bit for bit: no cracks), fragments beyond far are discarded.  near / far None: from the vertices' bounding
+    box (one host read), D the camera's distance to its centre and rho its half-diagonal, near = max(D - rho,
+    1e-3 rho), far = D + rho.  The contract (include/anerf.h) keeps every decision on integers: the result
+    does not depend on the schedule and is bit for bit that of `rasterize_mesh_camera_reference`.  ValueError before
+    anything is launched: rasterize_mesh's cases, near not finite or <= 0, far not finite or < near, a focal of 0.
+    Four launches on the current stream.  Out of scope: side-plane clipping (a triangle reaching beyond 2^20 pixels is
+    dropped, not cut), multisampling, back-face culling, writing image files."""
+    who = "rasterize_mesh_camera"
+    V, K = camera_view(c2w, H, W, focal, center)
+    V, K, nch, bg = _persp_args(_shape(vertices), V, K, W, H, _shape(attrs), background, who)
+    if near is not None and far is not None:
+        near, far = _camera_range(None, c2w, near, far, who)
+    p, t, a = _raster_inputs(vertices, triangles, attrs, who)
+    width, height = int(W), int(H)
+    with torch.cuda.device(t.device):
+        if near is None or far is None:
+            near, far = _camera_range(_bounding_box(p), c2w, near, far, who)
+        need = _lib.workspace("anerf_mesh_raster_persp_workspace", int(p.shape[0]), int(t.shape[0]), width, height)
+        ws = torch.empty(need, device=t.device, dtype=torch.uint8)
+        return _raster_persp_launch(p, t, V, K, near, far, width, height, a, nch, bg, ws)
+
+
+def _persp_polygons_reference(ct, near):
+    """The near-plane cut of the contract on camera-space triangles ct float32 [T, 3, 3] (xc, yc, d), all finite:
+    (nq int [T]: 0, 3 or 4 polygon vertices; Q float32 [T, 4, 3]; rows float32 [T, 4, 3] over the ORIGINAL vertices)."""
+    T = len(ct)
+    ar = np.arange(T)
+    IN = ct[..., 2] >= near
+    n_in = IN.sum(1)
+    s = np.zeros(T, np.int64)  # the IN vertex whose predecessor is not IN (0 when all or none are IN)
+    for k in range(3):
+        s = np.where(IN[:, k] & ~IN[:, (k + 2) % 3], k, s)
+    r = (s[:, None] + np.arange(3)) % 3
+    rot = ct[ar[:, None], r]  # the vertices from s on, in the triangle's order
+    unit = np.eye(3, dtype=_F)
+
+    def cut(i, o):  # from the IN end i to the OUT end o (places in `rot`)
+        t = (rot[:, i, 2] - near) / (rot[:, i, 2] - rot[:, o, 2])
+        q = np.stack([rot[:, i, 0] + t * (rot[:, o, 0] - rot[:, i, 0]),
+                      rot[:, i, 1] + t * (rot[:, o, 1] - rot[:, i, 1]), np.full(T, near, _F)], -1)
+        row = np.zeros((T, 3), _F)
+        row[:, i] = _F(1) - t
+        row[:, o] = t
+        return q.astype(_F), row
+
+    with np.errstate(all="ignore"):
+        c01, c02, c12 = cut(0, 1), cut(0, 2), cut(1, 2)
+    one, two = (n_in == 1)[:, None], (n_in == 2)[:, None]
+    Q = np.zeros((T, 4, 3), _F)
+    rows = np.zeros((T, 4, 3), _F)  # over the places in `rot`
+    Q[:, 0], rows[:, 0] = rot[:, 0], unit[0]
+    Q[:, 1], rows[:, 1] = np.where(one, c01[0], rot[:, 1]), np.where(one, c01[1], unit[1])
+    Q[:, 2] = np.where(one, c02[0], np.where(two, c12[0], rot[:, 2]))
+    rows[:, 2] = np.where(one, c02[1], np.where(two, c12[1], unit[2]))
+    Q[:, 3], rows[:, 3] = c02[0], c02[1]
+    back = np.empty_like(rows)  # place k of `rot` is the original vertex r[:, k]
+    for k in range(3):
+        back[ar, :, r[:, k]] = rows[:, :, k]
+    nq = np.where(n_in == 0, 0, np.where(n_in == 2, 4, 3))
+    return nq, Q, back
+
+
+_PERSP_SUBS = ((0, 1, 2), (0, 2, 3))  # the fan of the cut polygon
+
+
+def _persp_fragments_reference(X, Y, iw, a2, flip, far, sid, i, j):
+    """The contract's fragment of sub-triangles `sid` at pixels (i, j): (ok, u [n, 3], dep)."""
+    inside, b0, b1, b2 = _coverage_reference(X, Y, a2, flip, sid, i, j)
+    with np.errstate(all="ignore"):
+        u = np.stack([b0 * iw[sid, 0], b1 * iw[sid, 1], b2 * iw[sid, 2]], -1).astype(_F)
+        dep = (_F(1) / ((u[:, 0] + u[:, 1]) + u[:, 2])).astype(_F)
+        ok = inside & (dep > 0) & (dep <= far)
+    return ok, u, dep
+
+
+def _persp_setup_reference(p, tri, V, K, near, W, H):
+    """The contract's set-up of all 2 T sub-triangles (2 t + m is sub-triangle m of triangle t): snapped X, Y int64
+    [2 T, 3], iw float32 [2 T, 3], rows float32 [2 T, 3, 3] over the original vertices, a2, flip, the boxes i0, i1, j0,
+    j1, and draws bool [2 T]: the sub-triangle exists, has an area and a pixel centre in its box."""
+    nt = len(tri)
+    with np.errstate(all="ignore"):
+        c = np.stack([((V[k, 0] * p[:, 0] + V[k, 1] * p[:, 1]) + V[k, 2] * p[:, 2]) + V[k, 3]
+                      for k in range(3)], -1).astype(_F)[tri]  # [T, 3 vertices, (xc, yc, d)]
+        finite = np.isfinite(c).all(axis=(1, 2))
+        nq, Q, rows = _persp_polygons_reference(np.where(finite[:, None, None], c, _F(0)), near)
+        nq = np.where(finite, nq, 0)
+        s0 = K[0] * (Q[..., 0] / Q[..., 2]) + K[2]
+        s1 = K[1] * (Q[..., 1] / Q[..., 2]) + K[3]
+        iw4 = (_F(1) / Q[..., 2]).astype(_F)
+        used = np.arange(4)[None] < nq[:, None]
+        fine = (np.isfinite(s0) & np.isfinite(s1) & np.isfinite(iw4) & (np.abs(s0) <= _F(2.0 ** 20)) &
+                (np.abs(s1) <= _F(2.0 ** 20)))
+        good = (nq > 0) & (fine | ~used).all(1)
+        keep = good[:, None] & used
+        X4 = np.rint(np.where(keep, s0, _F(0)).astype(_F) * _F(256)).astype(np.int64)
+        Y4 = np.rint(np.where(keep, s1, _F(0)).astype(_F) * _F(256)).astype(np.int64)
+    sub = np.array(_PERSP_SUBS)
+    X, Y = X4[:, sub].reshape(2 * nt, 3), Y4[:, sub].reshape(2 * nt, 3)
+    iw = np.ascontiguousarray(iw4[:, sub].reshape(2 * nt, 3))
+    srows = rows[:, sub].reshape(2 * nt, 3, 3)
+    exists = (good[:, None] & (np.array([3, 4])[None] <= nq[:, None])).reshape(-1)
+    a2, flip, i0, i1, j0, j1 = _boxes_reference(X, Y, W, H)
+    draws = exists & (a2 != 0) & (i0 <= i1) & (j0 <= j1)
+    return X, Y, iw, srows, a2, flip, i0, i1, j0, j1, draws
+
+
+def _raster_persp_reference(p, tri, V, K, near, far, W, H, a, nch, bg):
+    """The checker on checked host arrays: MeshRaster of arrays."""
+    keys = np.full(H * W, _EMPTY_KEY, np.uint64)
+    nt = len(tri)
+    if nt:
+        X, Y, iw, srows, a2, flip, i0, i1, j0, j1, draws = _persp_setup_reference(p, tri, V, K, near, W, H)
+        for sid, i, j in _candidates_reference(np.nonzero(draws)[0], i0, i1, j0, j1):
+            ok, _, dep = _persp_fragments_reference(X, Y, iw, a2, flip, far, sid, i, j)
+            key = (dep[ok].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (sid[ok] >> 1).astype(np.uint64)
+            np.minimum.at(keys, (j[ok] * W + i[ok]), key)
+    hit = np.nonzero(keys != _EMPTY_KEY)[0]
+    face_ids = np.full(H * W, -1, np.int32)
+    depth = np.full(H * W, np.inf, _F)
+    bary = np.zeros((H * W, 3), _F)
+    image = None if a is None else np.tile(bg, (H * W, 1)).astype(_F)
+    if len(hit):
+        tid = (keys[hit] & np.uint64(0xffffffff)).astype(np.int64)
+        bits = (keys[hit] >> np.uint64(32)).astype(np.uint32)
+        done = np.zeros(len(hit), bool)
+        B = np.zeros((len(hit), 3), _F)
+        dd = np.zeros(len(hit), _F)
+        for m in range(2):  # the first sub-triangle that reproduces the key
+            sid = 2 * tid + m
+            ok, u, dep = _persp_fragments_reference(X, Y, iw, a2, flip, far, sid, hit % W, hit // W)
+            ok &= draws[sid] & (dep.view(np.uint32) == bits) & ~done
+            with np.errstate(all="ignore"):
+                g = (u * dep[:, None]).astype(_F)
+                r = srows[sid]
+                Bm = (g[:, 0, None] * r[:, 0] + g[:, 1, None] * r[:, 1]) + g[:, 2, None] * r[:, 2]
+            B[ok], dd[ok] = Bm[ok], dep[ok]
+            done |= ok
+        assert done.all()
+        face_ids[hit] = tid
+        depth[hit] = dd
+        bary[hit] = B
+        if a is not None:
+            with np.errstate(all="ignore"):
+                a0, a1, a2_ = a[tri[tid, 0]], a[tri[tid, 1]], a[tri[tid, 2]]
+                image[hit] = (B[:, 0, None] * a0 + B[:, 1, None] * a1) + B[:, 2, None] * a2_
+    return MeshRaster(face_ids.reshape(H, W), depth.reshape(H, W), bary.reshape(H, W, 3),
+                      None if image is None else image.reshape(H, W, nch))
+
+
+def rasterize_mesh_camera_reference(vertices, triangles, c2w, H, W, focal, center=None, near=None, far=None,
+                                    attrs=None, background=1.0):
+    """NumPy implementation of `rasterize_mesh_camera`'s contract: its checker.  Returns MeshRaster of arrays."""
+    who = "rasterize_mesh_camera_reference"
+    p = np.ascontiguousarray(_lib.host_array(vertices), dtype=_F)
+    a = None if attrs is None else np.ascontiguousarray(_lib.host_array(attrs), dtype=_F)
+    V, K = camera_view(c2w, H, W, focal, center)
+    V, K, nch, bg = _persp_args(p.shape, V, K, W, H, None if a is None else a.shape, background, who)
+    tri = _host_triangles(triangles, len(p), who)
+    near, far = _camera_range(_bounding_box(p) if near is None or far is None else None, c2w, near, far, who)
+    return _raster_persp_reference(p, tri, V, K, near, far, int(W), int(H), a, nch, bg)
+
+
+MeshViews = collections.namedtuple("MeshViews", ["rgb", "depth", "mask"])
+
+
+def _views_args(c2ws, focal, centers, who):
+    """Per frame (c2w, focal, center) of render_mesh_views: focal one value, [F] or [F, 2] (as rays.device_boxes takes
+    it; a sequence of F values is read per frame), centers None or [F, 2]."""
+    cs = np.asarray(_lib.host_array(c2ws), dtype=np.float64)
+    if cs.ndim != 3 or cs.shape[1:] not in ((3, 4), (4, 4)):
+        raise ValueError(f"{who}: c2ws must be [F, 3, 4] or [F, 4, 4], got shape {cs.shape}")
+    F = len(cs)
+    f = np.asarray(_lib.host_array(focal), dtype=np.float64)
+    if f.ndim == 0:
+        f = np.full(F, float(f))
+    if f.shape not in ((F,), (F, 2)):
+        raise ValueError(f"{who}: focal must be one value, [{F}] or [{F}, 2], got shape {f.shape}")
+    ce = None if centers is None else np.asarray(_lib.host_array(centers), dtype=np.float64)
+    if ce is not None and ce.shape != (F, 2):
+        raise ValueError(f"{who}: centers must be [{F}, 2], got shape {ce.shape}")
+    return [(cs[k], f[k], None if ce is None else ce[k]) for k in range(F)]
+
+
+@torch.no_grad()
+def render_mesh_views(vertices, triangles, c2ws, H, W, focal, centers=None, colors=None, near=None, far=None,
+                      background=1.0):
+    """The mesh at the render cameras: one `rasterize_mesh_camera` per camera of `c2ws` [F, 3, 4] or [F, 4, 4] --
+    render_path's poses, the dataset's -- with `focal` one value, [F] or [F, 2] and `centers` None or [F, 2].  Returns
+    MeshViews of device tensors: rgb uint8 [F, H, W, 3] to lay over the images, depth float32 [F, H, W] (camera
+    depth, +inf where empty) to set against render_rays' depth, mask bool [F, H, W] to set against a dataset mask or
+    acc.  `colors` and the conversion to uint8 are mesh_turntable's: None colours by normal (0.5 vertex_normals + 0.5),
+    or float [V, 3] in [0, 1], or uint8 [V, 3]; x becomes rint(255 clamp(x, 0, 1)).  near / far None: per camera from
+    the one bounding box (rasterize_mesh_camera).  One workspace serves all frames; the bounding box is the only host
+    read."""
+    who = "render_mesh_views"
+    v = torch.as_tensor(vertices)
+    _check_vertices(tuple(v.shape), who)
+    nv = int(v.shape[0])
+    cams = _views_args(c2ws, focal, centers, who)
+    _, nch, bg = _raster_args((nv, 3), np.zeros((3, 4), _F), W, H, (nv, 3), background, who)
+    t = _device_triangles(triangles, nv, who)
+    dev = t.device
+    width, height = int(W), int(H)
+    with torch.cuda.device(dev):
+        p = v.to(dev, torch.float32).contiguous()
+        c = _turntable_colors(colors, nv, who, lambda: _vertex_normals(p, t))
+        c = torch.as_tensor(c).to(dev, torch.float32).contiguous()
+        box = _bounding_box(p) if near is None or far is None else None
+        need = _lib.workspace("anerf_mesh_raster_persp_workspace", nv, int(t.shape[0]), width, height)
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        rgb = torch.empty((len(cams), height, width, 3), device=dev, dtype=torch.uint8)
+        depth = torch.empty((len(cams), height, width), device=dev, dtype=torch.float32)
+        mask = torch.empty((len(cams), height, width), device=dev, dtype=torch.bool)
+        for k, (c2w, f, centre) in enumerate(cams):
+            V, K = camera_view(c2w, height, width, f, centre)
+            V, K, _, _ = _persp_args((nv, 3), V, K, width, height, None, 0.0, who)
+            nr, fr = _camera_range(box, c2w, near, far, who)
+            r = _raster_persp_launch(p, t, V, K, nr, fr, width, height, c, nch, bg, ws)
+            rgb[k] = _to_uint8(r.image)
+            depth[k] = r.depth
+            mask[k] = r.face_ids >= 0
+    return MeshViews(rgb, depth, mask)
+
+
+def render_mesh_views_reference(vertices, triangles, c2ws, H, W, focal, centers=None, colors=None, near=None,
+                                far=None, background=1.0):
+    """NumPy implementation of `render_mesh_views` on the checkers: MeshViews of arrays."""
+    who = "render_mesh_views_reference"
+    p = np.ascontiguousarray(_lib.host_array(vertices), dtype=_F)
+    _check_vertices(p.shape, who)
+    cams = _views_args(c2ws, focal, centers, who)
+    c = _turntable_colors(None if colors is None else _lib.host_array(colors), len(p), who,
+                          lambda: vertex_normals_reference(p, triangles))
+    c = np.asarray(c, dtype=_F)
+    rgb = np.zeros((len(cams), int(H), int(W), 3), np.uint8)
+    depth = np.zeros((len(cams), int(H), int(W)), _F)
+    mask = np.zeros((len(cams), int(H), int(W)), bool)
+    for k, (c2w, f, centre) in enumerate(cams):
+        r = rasterize_mesh_camera_reference(p, triangles, c2w, H, W, f, centre, near, far, c, background)
+        rgb[k], depth[k], mask[k] = _to_uint8_reference(r.image), r.depth, r.face_ids >= 0
+    return MeshViews(rgb, depth, mask)
 
 
 # ------------------------------------------------------------------ vertex clustering

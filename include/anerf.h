@@ -34,6 +34,8 @@
  *   anerf_mesh_raster       what its OpenGL pass draws: an orthographic view of the mesh (ABI 24)   render_mesh.py:35-54, 164-182
  *   anerf_mesh_simplify_*   vertex clustering of that mesh on a grid of cells (ABI 25; the reference leaves decimation
  *                           to the user: trimesh with open3d or fast_simplification on the host)
+ *   anerf_mesh_raster_persp   that mesh through a perspective camera, cut at the near plane (ABI 26; the reference's
+ *                           viewer is orthographic: the mesh cannot be drawn where the field is rendered)
  *   anerf_radiance_points   the whole network (raw rgb, sigma) at points with their own directions (ABI 21)
  *                                                                              core/networks/nerf.py:133-148
  *   anerf_pose_kinematics   PoseOptLayer.calculate_kinematic, get_smpl_l2ws    core/pose_opt.py:372-521,
@@ -77,7 +79,7 @@
 extern "C" {
 #endif
 
-#define ANERF_ABI_VERSION 25
+#define ANERF_ABI_VERSION 26
 
 enum {
     ANERF_OK = 0,
@@ -577,6 +579,58 @@ int anerf_mesh_simplify_emit(const float* vertices, int64_t n_vertices, const in
                              const float* origin, float cell, const int32_t* dims, const void* ws, size_t ws_bytes,
                              float* out_vertices, int64_t n_out_v, int32_t* out_triangles, int64_t n_out_t,
                              int32_t* vertex_map, int32_t* representatives, void* stream);
+
+/* ABI 26: one view of such a mesh through a perspective (pinhole) camera, cut at the near plane: anerf_mesh_raster's
+ * outputs, integer coverage, 64-bit atomic-min depth test and small / large split (whose bits do not change), with a
+ * camera that can have vertices behind the eye, triangles across the near plane and interpolation that is not linear
+ * on the screen.  view: HOST float [3][4]; intrinsics: HOST float fx, fy, cx, cy; both read during the call.  fp32,
+ * every operation separately rounded, divisions correctly rounded; every decision is taken on integers or on one
+ * comparison of such values.
+ *   camera    c_k = ((V[k][0] x + V[k][1] y) + V[k][2] z) + V[k][3] gives (xc, yc, d): xc to the right, yc down the
+ *             image, d the distance along the optical axis, positive in front.  A triangle with an id outside
+ *             [0, n_vertices), or with any of its nine c not finite, draws nothing.
+ *   near      a vertex is IN iff d >= near.  No vertex IN: the triangle draws nothing.  All three IN: one sub-triangle,
+ *             the triangle itself (q0 q1 q2 = its vertices in its order).  One or two IN: the triangle is cut into a
+ *             polygon of 3 or 4 vertices, walked in the triangle's own vertex order from the IN vertex whose predecessor
+ *             is not IN -- with s that vertex, one IN: q = (v_s, cut(s, s+1), cut(s, s+2)); two IN: q = (v_s, v_s+1,
+ *             cut(s+1, s+2), cut(s, s+2)) (indices mod 3) -- and fanned from its first vertex into the sub-triangles
+ *             (q0 q1 q2) and (q0 q2 q3).  cut(I, O), always from the IN end I to the OUT end O whatever direction
+ *             the walk crosses the edge: t = (d_I - near) / (d_I - d_O); xc = xc_I + t (xc_O - xc_I), yc likewise,
+ *             d = near exactly -- a function of the two end points alone, so two triangles that share the edge get the
+ *             same bits: no cracks.  Every polygon vertex carries a row of weights over the ORIGINAL vertices: a unit
+ *             row for an original vertex, 1 - t at I, t at O and 0 at the third for a cut point.
+ *   project   per polygon vertex s_0 = fx (xc / d) + cx, s_1 = fy (yc / d) + cy, iw = 1 / d (d >= near > 0).  Pixel
+ *             centres, the snap X = (int64) rint(256 s_0), the 2^20 limit, the A2 == 0 rule, both windings, the edge
+ *             functions and the tie rule are anerf_mesh_raster's, per sub-triangle.  A triangle with a polygon vertex
+ *             whose s_0, s_1 or iw is not finite, or whose |s_0| or |s_1| exceeds 2^20, draws nothing at all; a
+ *             sub-triangle with A2 == 0 draws nothing itself.  There is no side-plane or guard-band clipping: a
+ *             triangle that reaches beyond 2^20 pixels is dropped, not cut.
+ *   fragment  b0, b1, b2: anerf_mesh_raster's screen barycentrics of the sub-triangle; u_k = b_k iw_k,
+ *             sum = (u_0 + u_1) + u_2, dep = 1 / sum.  The fragment is discarded unless 0 < dep <= far (a NaN is); near
+ *             is not tested again (the cut was the test: dep rounds to either side of near along the cut line).  The
+ *             pixel keeps the smallest key (bits(dep) << 32) | ORIGINAL triangle id (one 64-bit unsigned atomic min).
+ *   resolve   an empty pixel: anerf_mesh_raster's values.  Else the winning triangle's sub-triangles are tried in
+ *             order and the first whose fragment at the centre is kept with bits(dep) equal to the key's gives
+ *             g_k = u_k dep, B = (g_0 r_0 + g_1 r_1) + g_2 r_2 per component over its vertices' rows (all nine products
+ *             and six sums are taken), image[c] = (B_0 a_0[c] + B_1 a_1[c]) + B_2 a_2[c] over the ORIGINAL vertices.
+ * Outputs as anerf_mesh_raster's: face_ids the original triangle id, depth = dep, the camera depth d of the surface
+ * there (the parameter of the pixel's ray when its direction has d = 1; not a normalised z), +inf where empty; bary = B,
+ * perspective-correct weights over the original vertices; image the attributes under them.  The seam q0-q2 is an edge
+ * of both sub-triangles on the same snapped end points, so the tie rule gives a centre on it to one of them, as on an
+ * edge between two triangles.  A triangle whose sub-triangles' clipped boxes hold at most ANERF_RASTER_SMALL_PIXELS
+ * pixel centres together is drawn by the thread that set it up; a larger one goes onto the list once and its workgroups
+ * draw both sub-triangles: the same bits either way, on every run.  No side-plane clipping, no multisampling, no
+ * back-face culling.
+ * ws: anerf_mesh_raster_persp_workspace(n_vertices, n_tri, width, height) bytes (anerf_mesh_raster_workspace's layout
+ * and size), 8-byte aligned.  One frame per call; allocation-free, asynchronous on `stream`, no host read.
+ * ANERF_EINVAL, before any HIP call and naming the argument, for anerf_mesh_raster's cases, a NULL view or intrinsics,
+ * near not finite or <= 0, far not finite or < near, an intrinsic that is not finite, fx or fy equal to 0. */
+size_t anerf_mesh_raster_persp_workspace(int64_t n_vertices, int64_t n_tri, int32_t width, int32_t height);
+int anerf_mesh_raster_persp(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
+                            const float* view, const float* intrinsics, float near, float far, int32_t width,
+                            int32_t height, const float* attrs, int32_t n_channels, const float* background,
+                            int32_t* face_ids, float* depth, float* bary, float* image, void* ws, size_t ws_bytes,
+                            void* stream);
 
 /* ABI 21: raw network output at arbitrary points, every point with its own ray direction: raw_out [n][4] =
  * (rgb before the sigmoid, sigma before the density activation), the quantities of anerf_debug.raw_coarse /

@@ -32,7 +32,11 @@ body coloured by those normals under frame 7 of turntable_transforms; raster_lar
 cube's twelve triangles (the workgroups' path: the body's triangles are a pixel or two each and take the thread's);
 turntable_ms, mesh_turntable at its defaults (91 frames of 512 x 512, normals included); raster_reference_host_ms,
 rasterize_mesh_reference (NumPy) on the body's frame, once, for scale; the device frame is checked against it bit for
-bit.
+bit.  raster_persp_frame_ms is the same body in world coordinates (extract_mesh(coords="world", keep_largest=1)), 512 x
+512, coloured by its normals, through the camera of the benchmark's config-3 path (synthetic.make_scene's c2ws[0],
+focal 1.5 H) with near and far given: one rasterize_mesh_camera, next to raster_frame_ms of the same run;
+raster_persp_covered_pixels what it covers, raster_persp_reference_host_ms rasterize_mesh_camera_reference on that
+frame, once; the device frame is checked against it bit for bit.
 
 Simplification (meshops.simplify_mesh; csrc/anerf_simplify.hip), on the same filtered body in index coordinates from
 the origin (0, 0, 0), as extract_mesh(simplify=) runs it, at cell = 2 voxels and (the simplify4_* keys) cell = 4:
@@ -197,6 +201,27 @@ def _raster_legs(v, t):
             "raster_reference_host_ms": round(ref_ms, 1)}
 
 
+def _raster_persp_leg(rc, kps, skts, res, thr, sc):
+    """One frame of the body through the render path's perspective camera."""
+    v, t = rc.extract_mesh(kps, skts, None, radius=1.8, res=res, threshold=thr, coords="world", keep_largest=1)
+    colors = (meshops.vertex_normals(v, t) * 0.5 + 0.5).contiguous()
+    c2w, H, W, focal = sc["c2ws"][0], sc["H"], sc["W"], sc["focal"]
+    lo, hi = (x.double().cpu().numpy() for x in (v.amin(0), v.amax(0)))
+    D, rho = float(np.linalg.norm(c2w[:3, 3] - 0.5 * (lo + hi))), 0.5 * float(np.linalg.norm(hi - lo))
+    kw = dict(near=max(D - rho, 1e-3 * rho), far=D + rho, attrs=colors)  # (rasterize_mesh_camera's own defaults)
+    frame_ms, frame = _time(lambda: meshops.rasterize_mesh_camera(v, t, c2w, H, W, focal, **kw), reps=20)
+    t0 = time.perf_counter()
+    ref = meshops.rasterize_mesh_camera_reference(v.cpu().numpy(), t.cpu().numpy(), c2w, H, W, focal,
+                                                  **{**kw, "attrs": colors.cpu().numpy()})
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    for name in ("face_ids", "depth", "bary", "image"):
+        g, r = getattr(frame, name).cpu().numpy(), getattr(ref, name)
+        assert np.array_equal(g.view(np.int32), r.view(np.int32)), name
+    return {"raster_persp_frame_ms": round(frame_ms, 3),
+            "raster_persp_covered_pixels": int((frame.face_ids >= 0).sum()),
+            "raster_persp_reference_host_ms": round(ref_ms, 1)}
+
+
 def _simplify_legs(rc, kps, skts, res, thr, v, t):
     """Vertex clustering of the body (the mesh keep_largest=1 leaves), in index coordinates from the origin."""
     v, t = meshops.filter_mesh(v, t, keep_largest=1)
@@ -266,6 +291,7 @@ def main():
     legs = _filter_legs(rc, kps, skts, res, thr, v, ti, ni)
     legs.update(_smooth_legs(rc, kps, skts, res, thr, v, ti))
     legs.update(_raster_legs(v, ti))
+    legs.update(_raster_persp_leg(rc, kps, skts, res, thr, sc))
     legs.update(_simplify_legs(rc, kps, skts, res, thr, v, ti))
     n = (res + 1) ** 3
     line = json.dumps({"metric": "mesh path, res=%d, config3 fine net" % res, "precision": prec, "points": n,
