@@ -3,8 +3,11 @@
 #pragma once
 
 // ======================================================================= fused render kernel
-// The rays [ray0, ray0 + R) of one workgroup: both passes (or the launch's one) end to end.
-template <int W, int MR, int PREC>
+// The rays [ray0, ray0 + R) of one workgroup.  FUSED (single_net models, render_fused_kernel): both passes end to
+// end, composited and importance-sampled here.  Otherwise (render_kernel) the launch's one pass up to the raws, which
+// go to the workspace (A.raw_ws) for render_coarse_stage_kernel / render_fine_stage_kernel (anerf_kernels_small.hpp):
+// those stages are sequential double-precision chains on one lane, which this kernel (one wave per SIMD) cannot hide.
+template <int W, int MR, int PREC, bool FUSED>
 __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs& A, const LdsPlan& P,
                                             float* __restrict__ lds, int64_t ray0) {
     constexpr int WH = W / 2;
@@ -35,13 +38,14 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
     }
     stage_cut(M, lds + P.cut, tid);
     // coarse samples (sample_from_lineseg, ray_utils.py:218-224)
-    for (int idx = tid; idx < nr * S; idx += blockDim.x) {
-        const int r = idx / S, s = idx % S;
-        const float t = torch_linspace01(s, S);
-        const float nearv = lds[P.ray + 16 * r + 7], farv = lds[P.ray + 16 * r + 8];
-        lds[P.zc + P.z_stride * r + s] = lineseg_z(nearv, farv, t, A.lindisp != 0);
-    }
-    if (A.pass0 == 1) {  // fine-only launch: the sorted fine z of the coarse launch
+    if (FUSED || A.pass0 == 0)
+        for (int idx = tid; idx < nr * S; idx += blockDim.x) {
+            const int r = idx / S, s = idx % S;
+            const float t = torch_linspace01(s, S);
+            const float nearv = lds[P.ray + 16 * r + 7], farv = lds[P.ray + 16 * r + 8];
+            lds[P.zc + P.z_stride * r + s] = lineseg_z(nearv, farv, t, A.lindisp != 0);
+        }
+    if (!FUSED && A.pass0 == 1) {  // fine-only launch: the sorted fine z the coarse stage kernel left (P.zf == P.zc)
         // (16 B per lane: the item's nr x T floats are one contiguous run, rows 16-B aligned)
         if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(A.zf_ws) & 15) == 0) {
             const f32x4* src = reinterpret_cast<const f32x4*>(A.zf_ws + ray0 * T);
@@ -69,7 +73,7 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
         // single_net fine pass (raycasters.py:462-468): the same network on the I new samples only
         // (z_is, left by importance() in the ray's scratch at 6 z_stride), raws after the coarse ones
         // (cat([raw, raw_is]) order), merged by sorted_idx below; biases and G are still in LDS
-        const bool only_new = pass == 1 && M.single_net;
+        const bool only_new = FUSED && pass == 1 && M.single_net;
         if (!only_new) {
             stage_bias<W>(M, net, lds + P.bias, tid);  // (synced below)
             if (M.mrv == 0) compute_view_factor<WH, 0>(M, net, lds, P, nr, tid, st);
@@ -119,13 +123,15 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
             const int b = lockstep_mode<PREC>() ? bord[bi] : bi;
             const int r = b / nb, s0 = (b % nb) * 32;
             const float* zr = block_z(r);
-            float* rawr = lds + P.raw + P.raw_stride * r + (only_new ? 4 * S : 0);
-            mlp_block<W, MR, PREC>(M, net, lds + P.ray + 16 * r, lds + P.sk + P.sk_stride * r, lds + P.cut,
+            float* rawr = FUSED ? lds + P.raw + P.raw_stride * r + (only_new ? 4 * S : 0)
+                                : A.raw_ws + (ray0 + r) * n * 4;
+            mlp_block<W, MR, PREC, !FUSED>(M, net, lds + P.ray + 16 * r, lds + P.sk + P.sk_stride * r, lds + P.cut,
                              zr, nm, s0, lds + P.g + P.g_stride * r, rawr, lane, own ? A.mfma_count : nullptr,
                              lds + P.bias, (P.uf >= 0 && M.skip + 1 < M.D) ? lds + P.uf + wave * P.uf_stride : nullptr,
                              lds + P.wv + wave * P.wv_stride, st, own);
         }
         STAMP(st, 2 + 2 * pass);
+        if constexpr (!FUSED) break;  // (one pass per launch; the kernel's item loop has the barrier before the next item)
         __syncthreads();
         STAMP(st, 6);
         // ---- composite (+ importance sampling after the coarse pass); one wave per ray
@@ -188,22 +194,6 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
         __syncthreads();
         STAMP(st, 3 + 2 * pass);
     }
-    if (I > 0 && A.pass1 == 1) {  // coarse-only launch: hand the fine z over
-        // (non-temporal: 0.8 KB per ray streams through L2 and would evict weight groups; 16 B per lane where
-        // T % 4 == 0 -- whole 64-B lines per quarter wave instead of 4-B pieces)
-        if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(A.zf_ws) & 15) == 0) {
-            f32x4* dst = reinterpret_cast<f32x4*>(A.zf_ws + ray0 * T);
-            for (int idx = tid; idx < nr * T / 4; idx += blockDim.x) {
-                const int r = (4 * idx) / T, s = (4 * idx) % T;
-                __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(lds + P.zf + P.z_stride * r + s), dst + idx);
-            }
-        } else {
-            for (int idx = tid; idx < nr * T; idx += blockDim.x) {
-                const int r = idx / T, s = idx % T;
-                __builtin_nontemporal_store(lds[P.zf + P.z_stride * r + s], A.zf_ws + (ray0 + r) * T + s);
-            }
-        }
-    }
     STAMP_FLUSH(st, A.stamps);
 }
 
@@ -215,8 +205,8 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
 // of the frame while the stealing evens out the bands' different costs (round 3's static XCD bands
 // lost 5 % to exactly that imbalance); +3.6 % fp16x4, outputs bit-identical (an item's arithmetic does
 // not depend on the workgroup that runs it; one workgroup per item: removed, code in 914abec).
-template <int W, int MR, int PREC>
-__global__ __launch_bounds__(256, 1) void render_kernel(ModelDev M, RenderArgs A, LdsPlan P) {
+template <int W, int MR, int PREC, bool FUSED>
+__device__ __forceinline__ void render_items(const ModelDev& M, const RenderArgs& A, const LdsPlan& P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int64_t items = (A.n + A.R - 1) / A.R;
     int* const slot = reinterpret_cast<int*>(lds + P.bord) + 2 * P.bord_n;
@@ -236,9 +226,22 @@ __global__ __launch_bounds__(256, 1) void render_kernel(ModelDev M, RenderArgs A
         __syncthreads();
         const int item = slot[0];
         if (item < 0) break;
-        render_item<W, MR, PREC>(M, A, P, lds, (int64_t)item * A.R);
+        render_item<W, MR, PREC, FUSED>(M, A, P, lds, (int64_t)item * A.R);
         __syncthreads();
     }
+}
+
+// One pass (A.pass0) up to the raws: every model with two networks, and every model without importance sampling.
+template <int W, int MR, int PREC>
+__global__ __launch_bounds__(256, 1) void render_kernel(ModelDev M, RenderArgs A, LdsPlan P) {
+    render_items<W, MR, PREC, false>(M, A, P);
+}
+
+// single_net models: both passes, the composite and the importance sampling in one launch (the fine pass merges the
+// coarse raws in LDS by sorted_idx, so there is no second launch to cut at).
+template <int W, int MR, int PREC>
+__global__ __launch_bounds__(256, 1) void render_fused_kernel(ModelDev M, RenderArgs A, LdsPlan P) {
+    render_items<W, MR, PREC, true>(M, A, P);
 }
 
 // ======================================================================= density-only queries
@@ -509,5 +512,6 @@ __global__ __launch_bounds__(256, 1) void radiance_kernel(ModelDev M, RadianceAr
 #endif
 #define ANERF_F16_INSTANCES(KW)                       \
     ANERF_F16_SHAPES(KW, render_kernel, RenderArgs)   \
+    ANERF_F16_SHAPES(KW, render_fused_kernel, RenderArgs) \
     ANERF_F16_SHAPES(KW, density_kernel, DensityArgs) \
     ANERF_F16_SHAPES(KW, radiance_kernel, RadianceArgs)

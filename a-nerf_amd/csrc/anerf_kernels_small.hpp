@@ -1,5 +1,5 @@
 // anerf_kernels_small.hpp — the small __global__ kernels of anerf_render.hip: near/far + NaN fill, ray generation,
-// composition, encoding stage.  Not templates, so one unit defines them (anerf_render_f16.hip includes
+// the render call's per-ray stages (composite, importance sampling), composition, encoding stage.  Not templates, so one unit defines them (anerf_render_f16.hip includes
 // anerf_kernels.hpp without this file).
 #pragma once
 
@@ -99,6 +99,94 @@ __global__ void nan_fill_kernel(const float* __restrict__ rb, int stride, int64_
             far_io[i] = (means[1] != means[1]) ? r[7] : means[1];
         }
     }
+}
+
+// ======================================================================= per-ray stages of the render call
+// What follows a render_kernel launch (anerf_kernels.hpp), which ends at the raws in the workspace: raw2outputs and,
+// after the coarse launch, the importance sampling -- composite() and importance() of anerf_stages.hpp, the functions
+// render_fused_kernel runs in the kernel, on the same values in the same order.  Their transmittance product and cdf
+// sum are sequential double-precision chains on lane 0: here one wave per ray in 64-thread workgroups with a few KB of
+// LDS each, so a CU holds dozens of rays and the chains' latency is hidden (the render kernel is one wave per SIMD).
+// LDS: ray slot [16] (composite reads |d| at 9), z [zs], (coarse: zf [zs],) scratch [8 zs] as render_item's
+// (composite's w, wz, wc, fac, al, importance's scratch from zs on, the results at 7 zs); zs = pad32(S + I).
+__host__ __device__ inline int render_stage_lds_floats(int S, int I, bool coarse) {
+    return 16 + ((coarse && I > 0) ? 10 : 9) * pad32(S + I);
+}
+
+__device__ __forceinline__ void render_stage_maps(const float* res, int lane, int64_t i, float* __restrict__ o_rgb,
+                                                  float* __restrict__ o_disp, float* __restrict__ o_acc) {
+    if (lane < 5) {
+        const float v = res[lane];
+        if (lane < 3) {
+            if (o_rgb) o_rgb[3 * i + lane] = v;
+        } else if (lane == 3) {
+            if (o_disp) o_disp[i] = v;
+        } else if (o_acc) {
+            o_acc[i] = v;
+        }
+    }
+}
+
+// After the coarse launch: the coarse maps (the final ones when I == 0), alpha0, the coarse debug arrays, and the
+// sorted fine z into A.zf_ws for the fine launch.  The z list is rebuilt from near / far exactly as render_item does.
+__global__ __launch_bounds__(64) void render_coarse_stage_kernel(ModelDev M, RenderArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int64_t i = blockIdx.x;
+    const int lane = threadIdx.x, S = A.S, I = A.I, T = S + I;
+    const int zs = pad32(T);
+    float* ray = lds;
+    float* z = lds + 16;
+    float* zf = z + zs;  // (I > 0 only)
+    float* scr = I > 0 ? zf + zs : zf;
+    const float* src = A.rb + i * A.stride;
+    if (lane == 0) ray[9] = norm3(src[3], src[4], src[5]);
+    const float nearv = A.near[i], farv = A.far[i];
+    for (int s = lane; s < S; s += 64) z[s] = lineseg_z(nearv, farv, torch_linspace01(s, S), A.lindisp != 0);
+    wave_sync();
+    const float* raw = A.raw_ws + i * S * 4;
+    const bool final_pass = I == 0;
+    float* o_alpha = final_pass ? A.alpha : A.alpha0;
+    for (int s = lane; s < S; s += 64) {
+        if (A.dbg_z0) A.dbg_z0[i * S + s] = z[s];
+        if (A.dbg_raw0)
+            for (int c = 0; c < 4; ++c) A.dbg_raw0[(i * S + s) * 4 + c] = raw[4 * s + c];
+    }
+    float* res = scr + 7 * zs;
+    composite(M, ray, z, raw, S, scr, zs, true, lane, o_alpha ? o_alpha + i * S : nullptr, res);
+    render_stage_maps(res, lane, i, final_pass ? A.rgb : A.rgb0, final_pass ? A.disp : A.disp0,
+                      final_pass ? A.acc : A.acc0);
+    if (I > 0) {
+        if (A.dbg_w0)
+            for (int s = lane; s < S; s += 64) A.dbg_w0[i * S + s] = scr[s];
+        // (inlined at this call: as a call, the callee's register budget makes this a 280-register kernel with
+        // scratch, one wave per SIMD -- the occupancy these kernels exist for)
+        [[clang::always_inline]] importance(z, scr, S, I, zf, scr + zs, true, lane);
+        for (int s = lane; s < T; s += 64) A.zf_ws[i * T + s] = zf[s];
+    }
+}
+
+// After the fine launch: the final maps, alpha and the fine debug arrays from A.zf_ws and the fine raws.
+__global__ __launch_bounds__(64) void render_fine_stage_kernel(ModelDev M, RenderArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int64_t i = blockIdx.x;
+    const int lane = threadIdx.x, T = A.S + A.I;
+    const int zs = pad32(T);
+    float* ray = lds;
+    float* z = lds + 16;
+    float* scr = z + zs;
+    const float* src = A.rb + i * A.stride;
+    if (lane == 0) ray[9] = norm3(src[3], src[4], src[5]);
+    for (int s = lane; s < T; s += 64) z[s] = A.zf_ws[i * T + s];
+    wave_sync();
+    const float* raw = A.raw_ws + i * T * 4;
+    for (int s = lane; s < T; s += 64) {
+        if (A.dbg_z1) A.dbg_z1[i * T + s] = z[s];
+        if (A.dbg_raw1)
+            for (int c = 0; c < 4; ++c) A.dbg_raw1[(i * T + s) * 4 + c] = raw[4 * s + c];
+    }
+    float* res = scr + 7 * zs;
+    composite(M, ray, z, raw, T, scr, zs, true, lane, A.alpha ? A.alpha + i * T : nullptr, res);
+    render_stage_maps(res, lane, i, A.rgb, A.disp, A.acc);
 }
 
 // A frame's traced pixels: an explicit index list, or (idx == NULL) the row-major half-open box

@@ -1568,8 +1568,9 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
     return pre6;  // (bf16x6 / fp16x3: after_last's first groups are in the ring)
 }
 
-// One 32-sample block of one ray through a whole NeRF: raw (rgb, sigma) into LDS.
-template <int W, int MR, int P>
+// One 32-sample block of one ray through a whole NeRF: raw (rgb, sigma) into LDS, or (GRAW) into the workspace's
+// raw array (raw_out 16-byte aligned), one 16-byte store per sample.
+template <int W, int MR, int P, bool GRAW = false>
 __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __restrict__ ray,
                           const float* __restrict__ sk, const float* __restrict__ cut, const float* __restrict__ z,
                           int n, int s0,
@@ -1658,10 +1659,16 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
     }
     if (store && hh == 0 && s0 + sl < n) {
         float* o = raw_out + 4 * (s0 + sl);
-        o[0] = rgb[0];
-        o[1] = rgb[1];
-        o[2] = rgb[2];
-        o[3] = sig;
+        if constexpr (GRAW) {
+            // (non-temporal, as the zf_ws hand-off: the raws stream through L2 and must not evict weight groups)
+            const f32x4 v = {rgb[0], rgb[1], rgb[2], sig};
+            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o));
+        } else {
+            o[0] = rgb[0];
+            o[1] = rgb[1];
+            o[2] = rgb[2];
+            o[3] = sig;
+        }
     }
 }
 

@@ -5,8 +5,10 @@
 //   MFMA B operand -> 8x256 MLP on v_mfma_f32_32x32x2_f32 with activations resident in the
 //   accumulator/VGPR file across layers (the transposed product out^T = W^T in^T keeps each
 //   layer's accumulator layout directly usable as the next layer's B operand; weights are
-//   packed on the host in that permuted k order) -> alpha / rgb heads on the VALU ->
-//   compositing + sample_pdf + merge-sort per ray in LDS -> fine pass over all S+I samples.
+//   packed on the host in that permuted k order) -> alpha / rgb heads on the VALU -> raws.
+// A launch ends at the raws (workspace); compositing + sample_pdf + merge-sort per ray run in the small stage
+// kernels after it (anerf_kernels_small.hpp), then the fine launch over all S+I samples and its stage kernel.
+// single_net models alone keep those stages in the kernel (render_fused_kernel: one launch, both passes).
 // The view layer is factorised: its per-sample direction input dv = T_k(e_jc) * w'_j is
 // split into a per-ray matrix G[j][n] (computed once per ray in LDS) and the per-sample cutoff
 // weights w'_j, so the per-sample K of the view layer is W + NJ + 1 instead of W + 27 NJ.
@@ -18,7 +20,7 @@
 //   anerf_stages.hpp   per-ray stages: view factor G, compositing, importance sampling
 //   anerf_kernels.hpp  templated __global__ kernels (render, density, radiance); their fp16 instances are
 //                      compiled in anerf_render_f16.hip (MFMA results in VGPRs) and extern here
-//   anerf_kernels_small.hpp  the small __global__ kernels (near/far, rays, compose, encode)
+//   anerf_kernels_small.hpp  the small __global__ kernels (near/far, rays, per-ray render stages, compose, encode)
 //   anerf_pose.hpp     pose -> skeleton transforms (kinematic chain, inverse)
 //   anerf_boxes.hpp    bounding cylinder + 2-D pixel box per frame (kp_to_valid_rays)
 //   anerf_pack.hpp     host weight packing / model binding
@@ -284,10 +286,18 @@ static size_t ws_zf_bytes(int64_t n, int32_t n_samples, int32_t n_importance) {
     return n_importance > 0 ? (((size_t)n * (size_t)(n_samples + n_importance) * 4 + 255) & ~(size_t)255) : 0;
 }
 
+// the raws of a render launch that ends there (every model but single_net ones), 16 B per sample, for the stage kernel
+// that follows it: n x S x 4 floats after the coarse launch, n x T x 4 after the fine one, in the same bytes (the coarse
+// raws are dead once render_coarse_stage_kernel has run)
+static size_t ws_raw_bytes(const anerf_model* m, int64_t n, int32_t n_samples, int32_t n_importance) {
+    if (m && m->desc.single_net) return 0;
+    return ((size_t)n * (size_t)(n_samples + n_importance) * 16 + 255) & ~(size_t)255;
+}
+
 size_t anerf_workspace_size(const anerf_model* m, int64_t n_rays, int32_t n_samples, int32_t n_importance) {
-    (void)m;
     const int64_t n = n_rays > 0 ? n_rays : 1;
-    return ws_near_far_bytes(n) + ws_zf_bytes(n, n_samples, n_importance) + 256;  // (+ 2 x 8 queue counters)
+    return ws_near_far_bytes(n) + ws_zf_bytes(n, n_samples, n_importance) + ws_raw_bytes(m, n, n_samples, n_importance) +
+           256;  // (+ 2 x 8 queue counters)
 }
 
 static int launch_near_far(const float* rb, int stride, int64_t n, const float* cyls, const int32_t* ray_pose,
@@ -381,13 +391,30 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
     R = std::min(R, 8);
     const int W = m->desc.net_width;
     const int nj = m->desc.n_joints, mrv = layout_multires_views(m->desc.multires_views), D = m->desc.net_depth;
-    LdsPlan P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, true, m->md.bone_cut != 0);
-    if (P.total * 4 > 160 * 1024) P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, false, m->md.bone_cut != 0);
+    // single_net models composite and importance-sample in the kernel, both passes in one launch: their fine pass
+    // merges the coarse raws in LDS by sorted_idx, so there is no second launch to cut at.  It is the only case that
+    // keeps the in-kernel stage (render_fused_kernel); every other launch ends at the raws (render_kernel) and the
+    // per-ray stage kernels of anerf_kernels_small.hpp follow it, on the same composite() / importance().
+    const bool fused = m->desc.single_net != 0;
+    LdsPlan P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, true, m->md.bone_cut != 0, fused);
+    if (P.total * 4 > 160 * 1024)
+        P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, false, m->md.bone_cut != 0, fused);
     while (R > 1 && P.total * 4 > 160 * 1024) {
         R /= 2;
-        P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, false, m->md.bone_cut != 0);
+        P = make_plan(R, nj, W, S, T, mrv, m->ngh, D, m->njh2, false, m->md.bone_cut != 0, fused);
     }
     if (P.total * 4 > 160 * 1024) return fail(ANERF_EINVAL, "configuration exceeds the 160 KiB LDS budget");
+    const size_t stage_lds[2] = {sizeof(float) * render_stage_lds_floats(S, I, true),
+                                 sizeof(float) * render_stage_lds_floats(S, I, false)};
+    if (!fused) {
+        if (stage_lds[0] > 160 * 1024) return fail(ANERF_EINVAL, "configuration exceeds the 160 KiB LDS budget");
+        if (stage_lds[0] > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)render_coarse_stage_kernel,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds[0]));
+        if (I > 0 && stage_lds[1] > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void*)render_fine_stage_kernel,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds[1]));
+    }
 
     RenderArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -424,37 +451,51 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
     a.stamps = g_stamps;
 #endif
     // With importance sampling the coarse and the fine pass run as two launches: every CU then
-    // streams one network's weights at a time, which fit an XCD's 4 MB L2 (both together do not);
-    // the fine z lists (T floats per ray) go through the workspace.
-    // (single_net: one network, so one launch; the fine pass reuses the coarse raws, biases and G in LDS.  Both passes
-    // of two networks in one launch, the round-1 schedule: removed, code in 914abec)
-    const int pstep = (I > 0 && !m->desc.single_net) ? 1 : 2;
+    // streams one network's weights at a time, which fit an XCD's 4 MB L2 (both together do not).
+    // Each launch leaves its raws in the workspace (16 B per sample) and a stage kernel composites them; the one after
+    // the coarse launch also writes the fine z lists (T floats per ray) the fine launch reads.
+    // (single_net: one network, so one launch; the fine pass reuses the coarse raws, biases and G in LDS: see `fused`
+    // above.  Both passes of two networks in one launch, the round-1 schedule: removed, code in 914abec)
+    const int pstep = fused ? 2 : 1;
+    const int n_launch = fused ? 1 : (I > 0 ? 2 : 1);
     a.zf_ws = I > 0 ? reinterpret_cast<float*>((char*)workspace + ws_near_far_bytes(n_rays)) : nullptr;
+    a.raw_ws = fused ? nullptr
+                     : reinterpret_cast<float*>((char*)workspace + ws_near_far_bytes(n_rays) + ws_zf_bytes(n_rays, S, I));
     unsigned grid = (unsigned)((n_rays + R - 1) / R);
     unsigned* queues = reinterpret_cast<unsigned*>((char*)workspace + ws_near_far_bytes(n_rays) +
-                                                   ws_zf_bytes(n_rays, S, I));
+                                                   ws_zf_bytes(n_rays, S, I) + ws_raw_bytes(m, n_rays, S, I));
     int ncu = 256;  // persistent workgroups: as many as fit on the chip at once, items from the band queues
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     HIP_TRY(hipMemsetAsync(queues, 0, 2 * 8 * sizeof(unsigned), st));
     const size_t lds_bytes = (size_t)P.total * 4;
     const int mr = layout_multires(m->desc.multires);  // (the instance; smaller counts zero-padded, anerf_pack.hpp)
+#define ANERF_PICK(K, WW, MM)                                                  \
+    (precision == ANERF_PREC_BF16X3 ? K<WW, MM, 1>                             \
+     : precision == ANERF_PREC_BF16X6 ? K<WW, MM, 2>                           \
+     : precision == ANERF_PREC_FP16X3 ? K<WW, MM, 3>                           \
+     : precision == ANERF_PREC_FP16X4 ? K<WW, MM, 4> : K<WW, MM, 0>)
 #define ANERF_LAUNCH(WW, MM)                                                                         \
     do {                                                                                            \
-        auto kfn = precision == ANERF_PREC_BF16X3 ? render_kernel<WW, MM, 1>                       \
-                 : precision == ANERF_PREC_BF16X6 ? render_kernel<WW, MM, 2>                       \
-                 : precision == ANERF_PREC_FP16X3 ? render_kernel<WW, MM, 3>                       \
-                 : precision == ANERF_PREC_FP16X4 ? render_kernel<WW, MM, 4> : render_kernel<WW, MM, 0>; \
+        auto kfn = fused ? ANERF_PICK(render_fused_kernel, WW, MM) : ANERF_PICK(render_kernel, WW, MM); \
         HIP_TRY(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                     (int)lds_bytes));                                               \
         int nb = 1;                                                                                 \
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 256, lds_bytes) != hipSuccess || nb < 1) \
             nb = 1;                                                                                 \
         const unsigned g = std::min<unsigned>(grid, (unsigned)(ncu * nb));                          \
-        for (int p0 = 0; p0 < 2; p0 += pstep) {                                                     \
+        for (int p0 = 0; p0 < n_launch; ++p0) {                                                     \
             a.pass0 = p0;                                                                           \
             a.pass1 = p0 + pstep;                                                                   \
             a.queue = queues + 8 * p0;                                                              \
             hipLaunchKernelGGL(kfn, dim3(g), dim3(256), lds_bytes, st, m->md, a, P);               \
+            if (!fused) {                                                                           \
+                if (p0 == 0)                                                                        \
+                    hipLaunchKernelGGL(render_coarse_stage_kernel, dim3((unsigned)n_rays), dim3(64), stage_lds[0], st, \
+                                       m->md, a);                                                   \
+                else                                                                                \
+                    hipLaunchKernelGGL(render_fine_stage_kernel, dim3((unsigned)n_rays), dim3(64), stage_lds[1], st, \
+                                       m->md, a);                                                   \
+            }                                                                                       \
         }                                                                                           \
     } while (0)
     if (W == 256 && mr == 7) ANERF_LAUNCH(256, 7);
@@ -467,6 +508,7 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
 #endif
     else return fail(ANERF_EINVAL, "no kernel instance for this width / multires");
 #undef ANERF_LAUNCH
+#undef ANERF_PICK
     HIP_TRY(hipGetLastError());
     return ANERF_OK;
 }

@@ -117,7 +117,8 @@ struct RenderArgs {
     unsigned long long* mfma_count;
     unsigned long long* stamps;
     int pass0, pass1;  // passes [pass0, pass1) of this launch (0 coarse, 1 fine)
-    float* zf_ws;      // n x T: the fine pass's sorted z, handed from the coarse launch to the fine one
+    float* zf_ws;      // n x T: the fine pass's sorted z, written by render_coarse_stage_kernel for the fine launch
+    float* raw_ws;     // n x (this launch's samples) x 4: the raws of a launch that ends there, for the stage kernels
     int lindisp;       // sample_from_lineseg in inverse depth (ANERF_FLAG_LINDISP)
     unsigned* queue;   // this launch's 8 band counters (persistent workgroups) (workspace, zeroed before the launch)
 };
@@ -140,23 +141,27 @@ __device__ __forceinline__ void kp_inputs(int cut_to, int shift_in, float dist, 
     uf = shift_in ? u * (2.0f / c) - 1.0f : u;
 }
 
+// fused: the launch composites (and importance-samples) in the kernel (single_net models; render_fused_kernel).
+// Otherwise the launch ends at the raws (render_kernel): one z list per ray (a launch runs one pass), no raw area,
+// and the per-ray scratch holds the view factor's trig table only.
 __host__ __device__ inline LdsPlan make_plan(int R, int nj, int W, int S, int T, int mrv, int ngh, int D, int njh2,
-                                             bool with_uf, bool bone_cut) {
+                                             bool with_uf, bool bone_cut, bool fused) {
     LdsPlan p;
     const int wh = W / 2;
     const int nk = 1 + 2 * mrv;
     p.sk_stride = nj * 12;
     p.z_stride = pad32(T > S ? T : S);
-    p.raw_stride = p.z_stride * 4;
+    p.raw_stride = fused ? p.z_stride * 4 : 0;
     p.g_stride = 2 * ngh * wh;
-    int scr_a = 8 * p.z_stride;          // composite / importance scratch
+    int scr_a = fused ? 8 * p.z_stride : 0;  // composite / importance scratch
     int scr_b = ((3 * nk + 3) & ~3) * nj + 256;  // trig table for G + per-part bias partials (256 / WH parts x WH)
     p.scr_stride = (scr_a > scr_b ? scr_a : scr_b);
     int o = 0;
     p.ray = o; o += 16 * R;
     p.sk = o; o += p.sk_stride * R;
     p.zc = o; o += p.z_stride * R;
-    p.zf = o; o += p.z_stride * R;
+    p.zf = fused ? o : p.zc;  // (a launch that ends at the raws reads either the coarse or the fine list)
+    if (fused) o += p.z_stride * R;
     p.raw = o; o += p.raw_stride * R;
     p.g = o; o += p.g_stride * R;
     p.scr = o; o += p.scr_stride * R;

@@ -1,7 +1,10 @@
 """Summarise the rocprofv3 --pmc passes of tools/gpu_pmc.sh for render_kernel into one JSON
 (profiles/<round>_pmc.json).  HBM bytes follow MI355X_MICROARCH.md's rocprofv3 section:
 FETCH_SIZE is in KiB and counts half of the bytes of wide streaming reads on gfx950 (x2),
-WRITE_SIZE is exact (KiB).  Usage: python tools/pmc_summary.py gpurun_out OUT.json [label] [precision]"""
+WRITE_SIZE is exact (KiB).  The render launches end at the raws; the per-ray stage kernels that follow them in the
+same render_rays call (render_coarse_stage_kernel, render_fine_stage_kernel) read those raws back, so the call's HBM
+bytes are the render launches' plus the stage kernels': both are reported, and their sum.
+Usage: python tools/pmc_summary.py DIR OUT.json [label] [precision]   (DIR: where tools/gpu_pmc.sh wrote its passes)"""
 import csv
 import json
 import os
@@ -9,6 +12,21 @@ import sys
 
 
 PREC_TEMPLATE = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "fp16x3": 3, "fp16x4": 4}
+STAGE_KERNELS = ("render_coarse_stage_kernel", "render_fine_stage_kernel")  # one dispatch each per two-launch call
+
+
+def stage_bytes(base):
+    """HBM bytes of each stage kernel's last dispatch (the timed call's), 0 for a build without them."""
+    out = {}
+    for k in STAGE_KERNELS:
+        f = rows(os.path.join(base, "pmc_fetch", "run_counter_collection.csv"), k)
+        w = rows(os.path.join(base, "pmc_write", "run_counter_collection.csv"), k)
+        if not f or not w:
+            out[k] = 0
+            continue
+        fl, wl = f[max(f, key=int)], w[max(w, key=int)]
+        out[k] = int(2 * fl["FETCH_SIZE"] * 1024 + wl["WRITE_SIZE"] * 1024)
+    return out
 
 
 def rows(path, kernel="render_kernel"):
@@ -46,6 +64,7 @@ def main():
     w, _ = per_call(rows(os.path.join(base, "pmc_write", "run_counter_collection.csv"), kern), launches)
     s, _ = per_call(rows(os.path.join(base, "pmc_sq", "run_counter_collection.csv"), kern), launches)
     hbm = 2 * f["FETCH_SIZE"] * 1024 + w["WRITE_SIZE"] * 1024
+    stages = stage_bytes(base)
     clock = s["GRBM_GUI_ACTIVE"] / 8 / (s["ns"] * 1e-9) / 1e9
     busy = s["SQ_INSTS_MFMA"] / 1024 * 64 / (s["ns"] * 1e-9 * clock * 1e9)
     res = {
@@ -60,6 +79,9 @@ def main():
         "WRITE_SIZE_KB_per_launch": w["WRITE_SIZE"],
         "render_kernel_hbm_bytes_per_launch": int(hbm),
         "hbm_bytes_note": "2 x FETCH_SIZE x 1024 (gfx950 half-count correction) + WRITE_SIZE x 1024, per call",
+        "stage_kernels_hbm_bytes": stages,
+        "render_rays_call_hbm_bytes": int(hbm) + sum(stages.values()),
+        "call_bytes_note": "the render launches (raws written once, 16 B per sample) + the stage kernels that read them",
         "SQ_INSTS_MFMA": s["SQ_INSTS_MFMA"],
         "SQ_INSTS_VALU": s["SQ_INSTS_VALU"],
         "SQ_WAVES": s["SQ_WAVES"],

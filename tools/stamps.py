@@ -23,6 +23,9 @@ NAMES = {0: "prologue", 1: "view factor G (G + bias column)", 7: "  view factor:
          14: "  L0 u-part prologue", 15: "  v-part prologues (L0 + skip)",
          16: "  heads: view layer (+ alpha)", 17: "  heads: view-direction part", 13: "  heads: rgb head + stores",
          18: "  barrier wait before hidden layers (bf16x6)"}
+# stamped by render_fused_kernel only (single_net models): a two-launch call composites in the stage kernels of
+# anerf_kernels_small.hpp, which are not stamped, and these phases are absent from its report
+FUSED_ONLY = (3, 5, 6)
 
 
 def main():
@@ -48,6 +51,8 @@ def main():
     tot = v[0:24].sum()  # top-level phases + the MLP sub-phases (stamped separately)
     print(f"tau={tau} precision={prec}: total wave-cycles {tot:.3e}")
     for i, nm in NAMES.items():
+        if i in FUSED_ONLY and v[i] == 0:
+            continue
         print(f"{nm:34s} {100 * v[i] / tot:6.2f} %")
 
 
