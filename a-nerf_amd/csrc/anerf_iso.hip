@@ -282,11 +282,7 @@ int check_common(const char* who, const float* grid, int32_t n0, int32_t n1, int
         return failf(ANERF_EINVAL, "%s: %d x %d x %d grid points do not fit 31 bits", who, n0, n1, n2);
     if (flags & ~ISO_FLAGS)
         return failf(ANERF_EINVAL, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ISO_FLAGS));
-    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    if (ws_bytes < pl->bytes)
-        return failf(ANERF_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (anerf_isosurface_workspace)", who,
-                     ws_bytes, pl->bytes);
-    return ANERF_OK;
+    return check_workspace(who, ws, ws_bytes, pl->bytes, 8, ANERF_EWORKSPACE, "anerf_isosurface_workspace");
 }
 
 Grid make_grid(const float* grid, int32_t n0, int32_t n1, int32_t n2, const Plan& pl, float threshold, int32_t flags) {

@@ -19,12 +19,12 @@
 //                             triangle_kernel  the surviving triangles, ids through vertex_map (separate launch)
 //
 //   anerf_mesh_adjacency_count  adj_count_kernel   per triangle: the pairs it lists, counted per vertex (int atomics)
-//                             (scan)             the raw row offsets: tile sums, one workgroup, per-tile scan
+//                             (exclusive_scan)   the raw row offsets; the rows of more than 64 raw entries listed
 //                             adj_fill_kernel    the raw rows through per-vertex cursors, in arrival order
 //                             adj_rows_kernel    per vertex: a row of <= 64 raw entries sorted by its thread, the
-//                                                distinct count and the boundary flag from its runs; longer rows listed
+//                                                distinct count and the boundary flag from its runs
 //                             adj_long_rows_kernel   per listed row: one workgroup, a bitonic network (LDS or global)
-//                             (scan)             the distinct counts -> offsets, the totals
+//                             (exclusive_scan)   the distinct counts -> offsets, the totals
 //   anerf_mesh_adjacency_emit   adj_emit_kernel, adj_emit_long_kernel   the distinct entries of the sorted rows
 //   anerf_mesh_smooth         smooth_step_kernel per vertex: one Jacobi step over its CSR row; one launch per step
 // (the adjacency's contract and the reason for the launch per step: further down and DESIGN.md)
@@ -47,14 +47,15 @@
 //
 // Compaction keeps both outputs in their original relative order: count -> scan -> emit without atomics, the
 // pattern of anerf_scan.hpp (256 threads x 4 consecutive items per workgroup), whose tiles, block scan, scan_kernel,
-// workspace layout and host helpers this unit shares with anerf_iso.hip.
+// workspace layout and host helpers this unit shares with anerf_iso.hip.  The adjacency's rows are built with the row
+// toolkit of the same header (exclusive_scan, take_slot, the long-row list and its walk, bitonic_sort), which this
+// unit shares with anerf_simplify.hip; its own are the pairs, the short rows' insertion sort, LDS_ROW and the emit.
 #include "anerf_scan.hpp"
 
 namespace {
 
 constexpr int TALLY_THR = 1024;  // threads per workgroup of the two tallying kernels
 constexpr int TALLY_WAVES = TALLY_THR / 64;
-constexpr long long MAXN = 0x7fffffffll;
 
 __device__ __forceinline__ int ld_parent(const int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -110,10 +111,6 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
         a = p;
         p = -1;
     }
-}
-
-__device__ __forceinline__ bool in_range(int a, int b, int c, int nv) {
-    return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv;
 }
 
 __global__ __launch_bounds__(NTHR) void init_kernel(int* __restrict__ parent, int* __restrict__ tri_count,
@@ -313,39 +310,30 @@ int check_compact(const char* who, const uint8_t* keep, int64_t nv, const int32_
                      (long long)nt);
     if ((nv > 0 && !keep) || (nt > 0 && !tri) || !ws)
         return failf(ANERF_EINVAL, "%s: NULL keep, triangles or workspace", who);
-    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    if (ws_bytes < pl->bytes)
-        return failf(ANERF_EINVAL, "%s: workspace of %zu bytes, %zu needed (anerf_mesh_compact_workspace)", who,
-                     ws_bytes, pl->bytes);
-    return ANERF_OK;
+    return check_workspace(who, ws, ws_bytes, pl->bytes, 8, ANERF_EINVAL, "anerf_mesh_compact_workspace");
 }
 
 // ------------------------------------------------------------------ vertex adjacency (CSR)
 constexpr int SHORT_ROW = 64;         // the raw entries one thread sorts at most; longer rows go to a workgroup
 constexpr int LDS_ROW = 8192;         // the padded length up to which a long row's network runs over LDS (32 KB)
-constexpr int MAX_LONG_BLOCKS = 1024;  // workgroups of the long-row kernels (each strides over the list)
 
 // Workspace, in ints; everything whose size depends on V alone comes first, so that anerf_mesh_adjacency_emit
 // finds it without the triangle count:
-//   raw_off[V + 1] | cnt[V] | long_list[V] | n_long | block_sum[nb] | block_max[nb] | base[nb] | raw[6 T]
+//   raw_off[V + 1] | cnt[V] | long_list[V] | n_long | tiles[3 nb] (both scans') | raw[6 T]
 // cnt holds the listed pairs per vertex (count), counts down to 0 as the cursor of the fill, then holds the
 // distinct degree (the row kernels), which the second scan turns into `offsets`.
 struct AdjPlan {
-    int nblocks;
-    size_t raw_off, cnt, long_list, n_long, block_sum, block_max, base, raw;  // offsets in ints
+    size_t raw_off, cnt, long_list, n_long, tiles, raw;  // offsets in ints
 };
 
 bool adj_plan(int64_t nv, AdjPlan* pl) {
     if (nv < 0 || nv > MAXN) return false;
-    pl->nblocks = nv > 0 ? tiles_for(nv) : 1;  // (no vertices: offsets[0] and the totals are still written)
     size_t o = 0;
     pl->raw_off = o, o += (size_t)nv + 1;
     pl->cnt = o, o += (size_t)nv;
     pl->long_list = o, o += (size_t)nv;
     pl->n_long = o, o += 1;
-    pl->block_sum = o, o += (size_t)pl->nblocks;
-    pl->block_max = o, o += (size_t)pl->nblocks;
-    pl->base = o, o += (size_t)pl->nblocks;
+    pl->tiles = o, o += scan_ints((int)nv, true);  // (no vertices: offsets[0] and the totals are still written)
     pl->raw = o;
     return true;
 }
@@ -368,11 +356,11 @@ __global__ __launch_bounds__(NTHR) void adj_count_kernel(const int* __restrict__
     if (nc) atomicAdd(cnt + c, nc);
 }
 
-// cnt[x] counts down: every listed pair takes a slot of its own in row x, in arrival order (sorted afterwards).
+// Every listed pair takes a slot of its own in row x (cnt: its cursor), in arrival order (sorted afterwards).
 __device__ __forceinline__ void adj_put(int* cnt, const int* __restrict__ raw_off, int* __restrict__ raw, int x,
                                         int y) {
     if (x == y) return;
-    const int slot = atomicSub(cnt + x, 1) - 1;
+    const int slot = take_slot(cnt, x);
     if (slot >= 0) raw[raw_off[x] + slot] = y;  // (slot < the row's count: inside the row)
 }
 
@@ -391,18 +379,14 @@ __global__ __launch_bounds__(NTHR) void adj_fill_kernel(const int* __restrict__ 
 }
 
 // One thread per vertex: a row of at most SHORT_ROW raw entries is sorted in place (insertion sort) and walked once
-// for its distinct entries and for a run of length 1 (a pair listed once: a boundary edge); a longer row is put on
-// the list of adj_long_rows_kernel (in arrival order: each row is handled on its own, so the order does not show).
+// for its distinct entries and for a run of length 1 (a pair listed once: a boundary edge); a longer row is on the
+// list of adj_long_rows_kernel (the scan of the raw counts put it there).
 __global__ __launch_bounds__(NTHR) void adj_rows_kernel(const int* __restrict__ raw_off, int* __restrict__ raw, int nv,
-                                                        int* __restrict__ deg, unsigned char* __restrict__ boundary,
-                                                        int* __restrict__ long_list, int* n_long) {
+                                                        int* __restrict__ deg, unsigned char* __restrict__ boundary) {
     const long long v = (long long)blockIdx.x * NTHR + threadIdx.x;
     if (v >= nv) return;
     const int b = raw_off[v], n = raw_off[v + 1] - b;
-    if (n > SHORT_ROW) {
-        long_list[atomicAdd(n_long, 1)] = (int)v;  // (each vertex at most once: the index stays below nv)
-        return;
-    }
+    if (n > SHORT_ROW) return;
     int* r = raw + b;
     for (int i = 1; i < n; ++i) {
         const int x = r[i];
@@ -422,68 +406,30 @@ __global__ __launch_bounds__(NTHR) void adj_rows_kernel(const int* __restrict__ 
     boundary[v] = (unsigned char)bnd;
 }
 
-// Bitonic sorting network over a[0, n) by one workgroup, ascending, the row padded virtually to P = 2^lp >= n with
-// +infinity: every compare-exchange (l, r), l < r, of this form of the network leaves the smaller at l, so an
-// infinity at r >= n never moves and those pairs are skipped.  Stage s merges blocks of 2^s: pairs (i, block end - i)
-// first, then halving strides.  Only __syncthreads between the stages (over global memory as well: one workgroup,
-// one CU).  lp <= 31; every loop is bounded by P.
-__device__ __forceinline__ void compare_exchange(int* a, unsigned l, unsigned r, unsigned n) {
-    if (r >= n) return;
-    const int x = a[l], y = a[r];
-    if (x > y) {
-        a[l] = y;
-        a[r] = x;
-    }
-}
-
-__device__ __forceinline__ void bitonic_sort(int* a, unsigned n, int lp) {
-    const unsigned half = lp > 0 ? 1u << (lp - 1) : 0u;  // pairs per stage
-    for (int s = 1; s <= lp; ++s) {
-        const unsigned k = 1u << s, h = k >> 1;
-        for (unsigned t = threadIdx.x; t < half; t += NTHR) {
-            const unsigned first = (t >> (s - 1)) << s, in = t & (h - 1);
-            compare_exchange(a, first + in, first + (k - 1 - in), n);
-        }
-        __syncthreads();
-        for (int q = s - 2; q >= 0; --q) {
-            const unsigned j = 1u << q;
-            for (unsigned t = threadIdx.x; t < half; t += NTHR) {
-                const unsigned l = ((t >> q) << (q + 1)) + (t & (j - 1));
-                compare_exchange(a, l, l + j, n);
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// One workgroup per listed row (strided over the list, whose length is read from the device: no host read): sorted
-// by the network, over LDS where the padded row fits and in place over global memory where not; then the distinct
-// count and the boundary flag from the sorted row, every thread looking at its entries' two neighbours.
+// One workgroup per listed row (for_each_long_row): sorted by the bitonic network of anerf_scan.hpp, over LDS where
+// the padded row fits and in place over global memory where not; then the distinct count and the boundary flag from
+// the sorted row, every thread looking at its entries' two neighbours.
 __global__ __launch_bounds__(NTHR) void adj_long_rows_kernel(const int* __restrict__ raw_off, int* raw, int nv,
                                                              int* __restrict__ deg, unsigned char* __restrict__ boundary,
                                                              const int* __restrict__ long_list,
                                                              const int* __restrict__ n_long) {
     __shared__ int row[LDS_ROW];
     __shared__ int tally[2];
-    const int nl = min(*n_long, nv);
-    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // (uniform over the workgroup)
-        const int v = long_list[li];
-        if ((unsigned)v >= (unsigned)nv) continue;
+    for_each_long_row(long_list, n_long, nv, [&](int v) {
         const int b = raw_off[v];
         const unsigned n = (unsigned)max(raw_off[v + 1] - b, 0);
         int* g = raw + b;
-        int lp = 0;
-        while (lp < 31 && (1u << lp) < n) ++lp;
+        const int lp = padded_log2(n);
         const bool in_lds = (1u << lp) <= (unsigned)LDS_ROW;
         if (threadIdx.x == 0) tally[0] = tally[1] = 0;
         if (in_lds) {
             for (unsigned i = threadIdx.x; i < n; i += NTHR) row[i] = g[i];
             __syncthreads();
-            bitonic_sort(row, n, lp);
+            bitonic_sort(IntRow{row}, n, lp);
             for (unsigned i = threadIdx.x; i < n; i += NTHR) g[i] = row[i];
         } else {
             __syncthreads();
-            bitonic_sort(g, n, lp);
+            bitonic_sort(IntRow{g}, n, lp);
         }
         __syncthreads();  // (the row in global memory is complete for the whole workgroup)
         int d = 0, single = 0;
@@ -501,90 +447,7 @@ __global__ __launch_bounds__(NTHR) void adj_long_rows_kernel(const int* __restri
             boundary[v] = (unsigned char)tally[1];
         }
         __syncthreads();  // (row and tally are free for the next row)
-    }
-}
-
-// Exclusive scan of in[0, n) into out[0, n] (out[n]: the sum, which fits an int: at most 6 T < 2^31), the block-sum
-// pattern of anerf_scan.hpp on its tiles and block scan: per-tile sums (and maxima) -> one workgroup scans them ->
-// per-tile scan.  Kept here, not there: one int array, and the row maximum that becomes totals[1] rides along.
-__global__ __launch_bounds__(NTHR) void tile_reduce_kernel(const int* __restrict__ in, int n, int* __restrict__ block_sum,
-                                                           int* __restrict__ block_max) {
-    __shared__ int lds[NTHR];
-    __shared__ int mx;
-    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
-    int s = 0, m = 0;
-    for (int it = 0; it < ITEMS; ++it) {
-        if (first + it < n) {
-            const int x = in[first + it];
-            s += x;
-            m = max(m, x);
-        }
-    }
-    if (threadIdx.x == 0) mx = 0;
-    int total;
-    block_exclusive_scan(s, lds, total);  // (its barriers publish mx = 0)
-    atomicMax(&mx, m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        block_sum[blockIdx.x] = total;
-        block_max[blockIdx.x] = mx;
-    }
-}
-
-__global__ __launch_bounds__(NTHR) void base_scan_kernel(const int* __restrict__ block_sum,
-                                                         const int* __restrict__ block_max, int nblocks,
-                                                         int* __restrict__ base, int* __restrict__ last,
-                                                         long long* __restrict__ totals) {
-    __shared__ int lds[NTHR];
-    __shared__ int mx;
-    if (threadIdx.x == 0) mx = 0;
-    __syncthreads();
-    int carry = 0, m = 0;
-    for (int start = 0; start < nblocks; start += NTHR) {
-        const int b = start + threadIdx.x;
-        const int c = b < nblocks ? block_sum[b] : 0;
-        if (b < nblocks) m = max(m, block_max[b]);
-        int total;
-        const int e = block_exclusive_scan(c, lds, total);
-        if (b < nblocks) base[b] = carry + e;
-        carry += total;
-    }
-    atomicMax(&mx, m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *last = carry;
-        if (totals) {
-            totals[0] = carry;
-            totals[1] = mx;
-        }
-    }
-}
-
-__global__ __launch_bounds__(NTHR) void tile_scan_kernel(const int* __restrict__ in, int n, const int* __restrict__ base,
-                                                         int* __restrict__ out) {
-    __shared__ int lds[NTHR];
-    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
-    int x[ITEMS], s = 0;
-    for (int it = 0; it < ITEMS; ++it) {
-        x[it] = first + it < n ? in[first + it] : 0;
-        s += x[it];
-    }
-    int total;
-    int e = base[blockIdx.x] + block_exclusive_scan(s, lds, total);
-    for (int it = 0; it < ITEMS; ++it) {
-        if (first + it >= n) break;
-        out[first + it] = e;
-        e += x[it];
-    }
-}
-
-void adj_scan(const AdjPlan& pl, int* w, const int* in, int n, int* out, long long* totals, hipStream_t s) {
-    hipLaunchKernelGGL(tile_reduce_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, in, n, w + pl.block_sum,
-                       w + pl.block_max);
-    hipLaunchKernelGGL(base_scan_kernel, dim3(1), dim3(NTHR), 0, s, (const int*)(w + pl.block_sum),
-                       (const int*)(w + pl.block_max), pl.nblocks, w + pl.base, out + n, totals);
-    if (n > 0)
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(pl.nblocks), dim3(NTHR), 0, s, in, n, (const int*)(w + pl.base), out);
+    });
 }
 
 // A row of the emit pass: its bounds clamped to the part of the workspace that holds the raw rows (the emit entry
@@ -623,10 +486,7 @@ __global__ __launch_bounds__(NTHR) void adj_emit_long_kernel(const int* __restri
                                                              const int* __restrict__ offsets, int* __restrict__ neighbors,
                                                              long long max_neighbors) {
     __shared__ int lds[NTHR];
-    const int nl = min(*n_long, nv);
-    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // (uniform over the workgroup)
-        const int v = long_list[li];
-        if ((unsigned)v >= (unsigned)nv) continue;
+    for_each_long_row(long_list, n_long, nv, [&](int v) {
         const int b = clamp_raw(raw_off[v], raw_cap), n = clamp_raw(raw_off[v + 1], raw_cap) - b;
         const int* r = raw + b;
         const long long end = min((long long)offsets[v + 1], max_neighbors);
@@ -639,12 +499,7 @@ __global__ __launch_bounds__(NTHR) void adj_emit_long_kernel(const int* __restri
             if (first && pos >= 0 && pos < end) neighbors[pos] = r[i];
             carry += total;
         }
-    }
-}
-
-int long_blocks(long long raw_entries) {
-    const long long rows = raw_entries / (SHORT_ROW + 1);  // no more rows than this can be long
-    return (int)(rows < 1 ? 1 : (rows > MAX_LONG_BLOCKS ? MAX_LONG_BLOCKS : rows));
+    });
 }
 
 // ------------------------------------------------------------------ smoothing
@@ -716,12 +571,9 @@ int anerf_mesh_components(const int32_t* triangles, int64_t n_tri, int64_t n_ver
     if (n_vertices > 0 && (!root || !tri_count || !vert_count || !ws))
         return anerf_internal_fail(ANERF_EINVAL,
                                    "anerf_mesh_components: NULL root, tri_count, vert_count or workspace");
-    const size_t need = (size_t)n_vertices * sizeof(int);
-    if (ws_bytes < need)
-        return failf(ANERF_EINVAL, "anerf_mesh_components: workspace of %zu bytes, %zu needed "
-                     "(anerf_mesh_components_workspace)", ws_bytes, need);
-    if ((uintptr_t)ws % 4)
-        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_components: the workspace must be 4-byte aligned");
+    const int rc = check_workspace("anerf_mesh_components", ws, ws_bytes, (size_t)n_vertices * sizeof(int), 4,
+                                   ANERF_EINVAL, "anerf_mesh_components_workspace");
+    if (rc != ANERF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int nv = (int)n_vertices;
     int* parent = (int*)ws;
@@ -807,33 +659,31 @@ int anerf_mesh_adjacency_count(const int32_t* triangles, int64_t n_tri, int64_t 
     if (!offsets || !totals_dev || !ws || (n_tri > 0 && !triangles) || (n_vertices > 0 && !boundary))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: NULL offsets, totals or workspace, or "
                                                  "NULL triangles or boundary with a non-zero extent");
-    if ((uintptr_t)ws % 4)
-        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_count: the workspace must be 4-byte aligned");
-    const size_t need = (pl.raw + (size_t)6 * (size_t)n_tri) * sizeof(int);
-    if (ws_bytes < need)
-        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_count: workspace of %zu bytes, %zu needed "
-                     "(anerf_mesh_adjacency_workspace)", ws_bytes, need);
+    const int rc = check_workspace("anerf_mesh_adjacency_count", ws, ws_bytes,
+                                   (pl.raw + (size_t)6 * (size_t)n_tri) * sizeof(int), 4, ANERF_EINVAL,
+                                   "anerf_mesh_adjacency_workspace");
+    if (rc != ANERF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int nv = (int)n_vertices;
     const long long nt = (long long)n_tri;
     int* w = (int*)ws;
     int *raw_off = w + pl.raw_off, *cnt = w + pl.cnt, *long_list = w + pl.long_list, *n_long = w + pl.n_long;
-    int* raw = w + pl.raw;
+    int *tiles = w + pl.tiles, *raw = w + pl.raw;
     const bool pairs = nv > 0 && nt > 0;
     hipLaunchKernelGGL(adj_zero_kernel, dim3(nv > 0 ? blocks_for(nv) : 1), dim3(NTHR), 0, s, cnt, nv, n_long);
     if (pairs) hipLaunchKernelGGL(adj_count_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, cnt);
-    adj_scan(pl, w, cnt, nv, raw_off, nullptr, s);
+    exclusive_scan<false, SHORT_ROW>(cnt, nv, raw_off, tiles, nullptr, long_list, n_long, s);
     if (pairs)
         hipLaunchKernelGGL(adj_fill_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, cnt,
                            (const int*)raw_off, raw);
     if (nv > 0) {
         hipLaunchKernelGGL(adj_rows_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, (const int*)raw_off, raw, nv, cnt,
-                           boundary, long_list, n_long);
+                           boundary);
         if (6 * nt > SHORT_ROW)
-            hipLaunchKernelGGL(adj_long_rows_kernel, dim3(long_blocks(6 * nt)), dim3(NTHR), 0, s, (const int*)raw_off,
-                               raw, nv, cnt, boundary, (const int*)long_list, (const int*)n_long);
+            hipLaunchKernelGGL(adj_long_rows_kernel, dim3(long_blocks(6 * nt, SHORT_ROW)), dim3(NTHR), 0, s,
+                               (const int*)raw_off, raw, nv, cnt, boundary, (const int*)long_list, (const int*)n_long);
     }
-    adj_scan(pl, w, cnt, nv, offsets, (long long*)totals_dev, s);
+    exclusive_scan<true, 0>(cnt, nv, offsets, tiles, (long long*)totals_dev, nullptr, nullptr, s);
     return launched("anerf_mesh_adjacency_count");
 }
 
@@ -846,11 +696,9 @@ int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, con
     if (!offsets || !ws || (max_neighbors > 0 && !neighbors))
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: NULL offsets or workspace, or NULL "
                                                  "neighbors with a non-zero capacity");
-    if ((uintptr_t)ws % 4)
-        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_adjacency_emit: the workspace must be 4-byte aligned");
-    if (ws_bytes < pl.raw * sizeof(int))
-        return failf(ANERF_EINVAL, "anerf_mesh_adjacency_emit: workspace of %zu bytes, at least %zu needed "
-                     "(anerf_mesh_adjacency_workspace)", ws_bytes, pl.raw * sizeof(int));
+    const int rc = check_workspace("anerf_mesh_adjacency_emit", ws, ws_bytes, pl.raw * sizeof(int), 4, ANERF_EINVAL,
+                                   "anerf_mesh_adjacency_workspace", "at least ");
+    if (rc != ANERF_OK) return rc;
     const int nv = (int)n_vertices;
     if (nv == 0 || max_neighbors == 0) return ANERF_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -860,8 +708,8 @@ int anerf_mesh_adjacency_emit(int64_t n_vertices, void* ws, size_t ws_bytes, con
     hipLaunchKernelGGL(adj_emit_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, w + pl.raw_off, w + pl.raw, nv, raw_cap,
                        offsets, neighbors, (long long)max_neighbors);
     if (raw_cap > SHORT_ROW)
-        hipLaunchKernelGGL(adj_emit_long_kernel, dim3(long_blocks(raw_cap)), dim3(NTHR), 0, s, w + pl.raw_off,
-                           w + pl.raw, nv, raw_cap, w + pl.long_list, w + pl.n_long, offsets, neighbors,
+        hipLaunchKernelGGL(adj_emit_long_kernel, dim3(long_blocks(raw_cap, SHORT_ROW)), dim3(NTHR), 0, s,
+                           w + pl.raw_off, w + pl.raw, nv, raw_cap, w + pl.long_list, w + pl.n_long, offsets, neighbors,
                            (long long)max_neighbors);
     return launched("anerf_mesh_adjacency_emit");
 }

@@ -36,7 +36,6 @@
 
 namespace {
 
-constexpr long long MAXN = 0x7fffffffll;
 constexpr int MAX_DIM = 16384;       // width, height
 constexpr int MAX_CH = 8;            // attribute channels
 constexpr int SNAP = 256;            // sub-pixel steps per pixel
@@ -47,10 +46,6 @@ constexpr int TILE_W = 64, TILE_H = NTHR / TILE_W;  // a wave's 64 keys are 512 
 constexpr unsigned long long EMPTY = ~0ull;
 constexpr float QUANT = 1073741824.f;  // 2^30
 constexpr float NORMAL_EPS = 1e-8f;    // the viewer's normalize_v3
-
-__device__ __forceinline__ bool in_range(int a, int b, int c, int nv) {
-    return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv;
-}
 
 // ------------------------------------------------------------------ vertex normals
 // v / max(|v|, 1e-8), |v| = sqrt((x x + y y) + z z), every operation separately rounded.
@@ -531,12 +526,9 @@ int raster_check(const char* who, const float* vertices, int64_t n_vertices, con
     if (n_channels > 0 && n_vertices > 0 && !attrs) return failf(ANERF_EINVAL, "%s: NULL attrs", who);
     if (n_channels > 0 && !background) return failf(ANERF_EINVAL, "%s: NULL background", who);
     if (n_channels > 0 && !image) return failf(ANERF_EINVAL, "%s: NULL image", who);
-    if (!ws) return failf(ANERF_EINVAL, "%s: NULL workspace", who);
-    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    if (ws_bytes < pl->bytes)
-        return failf(ANERF_EINVAL, "%s: workspace of %zu bytes, %zu needed (%s_workspace)", who, ws_bytes, pl->bytes,
-                     who);
-    return ANERF_OK;
+    char sizer[64];
+    snprintf(sizer, sizeof sizer, "%s_workspace", who);
+    return check_workspace(who, ws, ws_bytes, pl->bytes, 8, ANERF_EINVAL, sizer);
 }
 
 Scene raster_scene(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_tri,
@@ -580,13 +572,10 @@ int anerf_mesh_vertex_normals(const float* vertices, int64_t n_vertices, const i
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_vertex_normals: NULL normals");
     if (n_tri > 0 && !triangles)
         return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_vertex_normals: NULL triangles");
-    if (!ws) return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_vertex_normals: NULL workspace");
-    if ((uintptr_t)ws % 8)
-        return anerf_internal_fail(ANERF_EINVAL, "anerf_mesh_vertex_normals: the workspace must be 8-byte aligned");
-    const size_t need = anerf_mesh_vertex_normals_workspace(n_vertices, n_tri);
-    if (ws_bytes < need)
-        return failf(ANERF_EINVAL, "anerf_mesh_vertex_normals: workspace of %zu bytes, %zu needed "
-                     "(anerf_mesh_vertex_normals_workspace)", ws_bytes, need);
+    const int rc = check_workspace("anerf_mesh_vertex_normals", ws, ws_bytes,
+                                   anerf_mesh_vertex_normals_workspace(n_vertices, n_tri), 8, ANERF_EINVAL,
+                                   "anerf_mesh_vertex_normals_workspace");
+    if (rc != ANERF_OK) return rc;
     if (n_vertices == 0) return ANERF_OK;
     hipStream_t s = (hipStream_t)stream;
     const int nv = (int)n_vertices;

@@ -12,8 +12,7 @@
 //                                                 cell and 1 added to the representative's 64-bit sums and count
 //                              owner_count_kernel per triangle that neither leaves the mesh nor collapses: its owner,
 //                                                 the smallest of its three representatives, counts one row entry
-//                              (scan)             the row offsets: rows_count_kernel, scan_kernel, rows_offsets_kernel
-//                                                 (which also lists the rows longer than SHORT_ROW)
+//                              (exclusive_scan)   the row offsets; the rows longer than SHORT_ROW listed
 //                              fill_rows_kernel   the rows through per-owner cursors, in arrival order: an entry is
 //                                                 ((mid << 32) | max of the representatives, the triangle's index)
 //                              dedup_kernel       per triangle of a short row: it survives iff no entry of its row has
@@ -37,15 +36,17 @@
 // no table word and is never dereferenced; a triangle with an id outside [0, V) or a vertex without a cell is dropped
 // before any of its ids is used as an index.  The emit pass reads rep and the flags from the workspace and guards
 // every index it takes from them.
+//
+// The owner rows are built with the row toolkit of anerf_scan.hpp (exclusive_scan, take_slot, the long-row list and
+// its walk, bitonic_sort on KeyIndexRow), which this unit shares with the adjacency of anerf_mesh.hip; the two output
+// lists go through the header's count -> scan -> emit pattern (ScanSpace), as in anerf_iso.hip.
 #include "anerf_scan.hpp"
 
 namespace {
 
-constexpr long long MAXN = 0x7fffffffll;
 constexpr long long MAX_CELLS = 1ll << 26;  // include/anerf.h ANERF_SIMPLIFY_MAX_CELLS
 constexpr int NO_VERTEX = 0x7fffffff;      // an empty cell of the table
 constexpr int SHORT_ROW = 32;              // the entries up to which a row is searched by its triangles' own threads
-constexpr int MAX_LONG_BLOCKS = 1024;      // workgroups of long_rows_kernel (each strides over the list)
 constexpr float FIX = 1048576.f;           // 2^20: the fixed point of a vertex's offset in its cell
 
 struct Grid {
@@ -138,45 +139,7 @@ __global__ __launch_bounds__(NTHR) void owner_count_kernel(const int* __restrict
     if (triangle_row(tri, i, nv, rep, owner, key)) atomicAdd(row_cnt + owner, 1);
 }
 
-__global__ __launch_bounds__(NTHR) void rows_count_kernel(const int* __restrict__ row_cnt, int nv,
-                                                          int* __restrict__ block_counts, int nblocks) {
-    __shared__ int lds[NTHR];
-    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
-    int n = 0;
-    for (int it = 0; it < ITEMS; ++it) n += first + it < nv ? row_cnt[first + it] : 0;
-    int total;
-    block_exclusive_scan(n, lds, total);
-    if (threadIdx.x == 0) {
-        block_counts[blockIdx.x] = total;
-        block_counts[nblocks + blockIdx.x] = 0;  // (the scan's second list is not used here)
-    }
-}
-
-__global__ __launch_bounds__(NTHR) void rows_offsets_kernel(const int* __restrict__ row_cnt, int nv,
-                                                            const long long* __restrict__ base,
-                                                            const long long* __restrict__ row_total,
-                                                            int* __restrict__ row_off, int* __restrict__ long_list,
-                                                            int* n_long) {
-    __shared__ int lds[NTHR];
-    const long long first = (long long)blockIdx.x * TILE + threadIdx.x * ITEMS;
-    int x[ITEMS], n = 0;
-    for (int it = 0; it < ITEMS; ++it) {
-        x[it] = first + it < nv ? row_cnt[first + it] : 0;
-        n += x[it];
-    }
-    int total;
-    int e = (int)base[blockIdx.x] + block_exclusive_scan(n, lds, total);  // (at most n_tri: fits an int)
-    for (int it = 0; it < ITEMS; ++it) {
-        const long long v = first + it;
-        if (v >= nv) break;
-        row_off[v] = e;
-        e += x[it];
-        if (x[it] > SHORT_ROW) long_list[atomicAdd(n_long, 1)] = (int)v;  // (each vertex at most once: below nv)
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) row_off[nv] = (int)row_total[0];
-}
-
-// row_cnt[owner] counts down: every entry takes a slot of its own in the owner's row, in arrival order.
+// Every entry takes a slot of its own in its owner's row (row_cnt: its cursor), in arrival order.
 __global__ __launch_bounds__(NTHR) void fill_rows_kernel(const int* __restrict__ tri, long long nt, int nv,
                                                          const int* __restrict__ rep, int* row_cnt,
                                                          const int* __restrict__ row_off,
@@ -187,7 +150,7 @@ __global__ __launch_bounds__(NTHR) void fill_rows_kernel(const int* __restrict__
     int owner;
     unsigned long long key;
     if (!triangle_row(tri, i, nv, rep, owner, key)) return;
-    const int slot = atomicSub(row_cnt + owner, 1) - 1;
+    const int slot = take_slot(row_cnt, owner);
     if (slot < 0) return;  // (slot < the row's count: inside the row)
     const long long at = (long long)row_off[owner] + slot;
     if (at >= nt) return;
@@ -220,66 +183,26 @@ __global__ __launch_bounds__(NTHR) void dedup_kernel(const int* __restrict__ tri
     flag[i] = keep;
 }
 
-// The bitonic network of the adjacency unit (anerf_mesh.hip) on (key, index) pairs: every compare-exchange (l, r),
-// l < r, leaves the smaller at l, so the virtual +infinity padding at r >= n never moves and those pairs are skipped.
-__device__ __forceinline__ void compare_exchange(unsigned long long* k, int* x, unsigned l, unsigned r, unsigned n) {
-    if (r >= n) return;
-    const unsigned long long kl = k[l], kr = k[r];
-    const int xl = x[l], xr = x[r];
-    if (kl > kr || (kl == kr && xl > xr)) {
-        k[l] = kr;
-        k[r] = kl;
-        x[l] = xr;
-        x[r] = xl;
-    }
-}
-
-__device__ __forceinline__ void bitonic_sort(unsigned long long* k, int* x, unsigned n, int lp) {
-    const unsigned half = lp > 0 ? 1u << (lp - 1) : 0u;  // pairs per stage
-    for (int s = 1; s <= lp; ++s) {
-        const unsigned w = 1u << s, h = w >> 1;
-        for (unsigned t = threadIdx.x; t < half; t += NTHR) {
-            const unsigned first = (t >> (s - 1)) << s, in = t & (h - 1);
-            compare_exchange(k, x, first + in, first + (w - 1 - in), n);
-        }
-        __syncthreads();
-        for (int q = s - 2; q >= 0; --q) {
-            const unsigned j = 1u << q;
-            for (unsigned t = threadIdx.x; t < half; t += NTHR) {
-                const unsigned l = ((t >> q) << (q + 1)) + (t & (j - 1));
-                compare_exchange(k, x, l, l + j, n);
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// One workgroup per listed row (strided over the list, whose length is read from the device): sorted in place over
-// global memory (one workgroup, one CU: __syncthreads between the stages), then the first entry of every run of a key
-// -- its smallest index -- survives.
+// One workgroup per listed row (for_each_long_row): sorted by (key, index) in place over global memory by the bitonic
+// network of anerf_scan.hpp, then the first entry of every run of a key -- its smallest index -- survives.
 __global__ __launch_bounds__(NTHR) void long_rows_kernel(const int* __restrict__ row_off, unsigned long long* keys,
                                                          int* idx, int nv, long long nt,
                                                          const int* __restrict__ long_list,
                                                          const int* __restrict__ n_long, int* __restrict__ flag) {
-    const int nl = min(*n_long, nv);
-    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // (uniform over the workgroup)
-        const int v = long_list[li];
-        if ((unsigned)v >= (unsigned)nv) continue;
+    for_each_long_row(long_list, n_long, nv, [&](int v) {
         const long long b = row_off[v], e = row_off[v + 1];
-        if (b < 0 || e > nt || e <= b) continue;
+        if (b < 0 || e > nt || e <= b) return;  // (uniform over the workgroup)
         const unsigned n = (unsigned)(e - b);
         unsigned long long* k = keys + b;
         int* x = idx + b;
-        int lp = 0;
-        while (lp < 31 && (1u << lp) < n) ++lp;
         __syncthreads();
-        bitonic_sort(k, x, n, lp);
+        bitonic_sort(KeyIndexRow{k, x}, n, padded_log2(n));
         __syncthreads();
         for (unsigned i = threadIdx.x; i < n; i += NTHR) {
             const int t = x[i];
             if ((unsigned)t < (unsigned)nt) flag[t] = (i == 0 || k[i - 1] != k[i]) ? 1 : 0;
         }
-    }
+    });
 }
 
 __global__ __launch_bounds__(NTHR) void out_count_kernel(const int* __restrict__ rep, long long nv,
@@ -379,22 +302,19 @@ __global__ __launch_bounds__(NTHR) void triangles_kernel(const int* __restrict__
 
 // ------------------------------------------------------------------ host
 // Workspace: the scan of the outputs (base | block_counts over the tiles of max(V, T): emit finds it at ws itself) |
-// the scan of the rows (over the tiles of V) | row_total[2] | sums[3 V] | keys[T]  (64-bit, then ints:)
-// | table[cells] | rep[V] | cnt[V] | row_cnt[V] | row_off[V + 1] | long_list[V] | n_long | flag[T] | idx[T]
+// sums[3 V] | keys[T]  (64-bit, then ints:) | table[cells] | rep[V] | cnt[V] | row_cnt[V] | row_off[V + 1] |
+// long_list[V] | n_long | tiles (the scan of the rows', over the tiles of V) | flag[T] | idx[T]
 struct Plan {
-    ScanSpace out, rows;
-    size_t rows_at, row_total, sums, keys, table, rep, cnt, row_cnt, row_off, long_list, n_long, flag, idx, bytes;
+    ScanSpace out;
+    size_t sums, keys, table, rep, cnt, row_cnt, row_off, long_list, n_long, tiles, flag, idx, bytes;
 };
 
 bool plan(int64_t nv, int64_t nt, int64_t cells, Plan* pl) {
     if (nv < 0 || nt < 0 || nv > MAXN || nt > MAXN || cells < 1 || cells > MAX_CELLS) return false;
-    const int nb = tiles_for(nv > nt ? nv : nt), nbv = tiles_for(nv);
+    const int nb = tiles_for(nv > nt ? nv : nt);
     pl->out = scan_space(nb < 1 ? 1 : nb);  // (empty lists still get their totals written)
-    pl->rows = scan_space(nbv < 1 ? 1 : nbv);
     const size_t V = (size_t)nv, T = (size_t)nt;
     size_t o = pl->out.bytes;
-    pl->rows_at = o, o += pl->rows.bytes;
-    pl->row_total = o, o += 2 * sizeof(long long);
     pl->sums = o, o += 3 * V * sizeof(long long);
     pl->keys = o, o += T * sizeof(long long);
     pl->table = o, o += (size_t)cells * sizeof(int);
@@ -404,15 +324,11 @@ bool plan(int64_t nv, int64_t nt, int64_t cells, Plan* pl) {
     pl->row_off = o, o += (V + 1) * sizeof(int);
     pl->long_list = o, o += V * sizeof(int);
     pl->n_long = o, o += sizeof(int);
+    pl->tiles = o, o += scan_ints((int)nv, false) * sizeof(int);
     pl->flag = o, o += T * sizeof(int);
     pl->idx = o, o += T * sizeof(int);
     pl->bytes = (o + 7) & ~(size_t)7;
     return true;
-}
-
-template <typename T>
-T* at(const void* ws, size_t off) {
-    return (T*)((char*)ws + off);
 }
 
 int check(const char* who, const float* vertices, int64_t nv, const int32_t* tri, int64_t nt, const float* origin,
@@ -436,21 +352,12 @@ int check(const char* who, const float* vertices, int64_t nv, const int32_t* tri
         return failf(ANERF_EINVAL, "%s: dims (%d, %d, %d) must be >= 1 with a product in [1, 2^26] "
                      "(ANERF_SIMPLIFY_MAX_CELLS)", who, (int)dims[0], (int)dims[1], (int)dims[2]);
     plan(nv, nt, cells, pl);
-    if ((uintptr_t)ws % 8) return failf(ANERF_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    if (ws_bytes < pl->bytes)
-        return failf(ANERF_EINVAL, "%s: workspace of %zu bytes, %zu needed (anerf_mesh_simplify_workspace)", who,
-                     ws_bytes, pl->bytes);
     for (int a = 0; a < 3; ++a) {
         g->o[a] = origin[a];
         g->n[a] = dims[a];
     }
     g->cell = cell;
-    return ANERF_OK;
-}
-
-int long_blocks(long long entries) {
-    const long long rows = entries / (SHORT_ROW + 1);  // no more rows than this can be long
-    return (int)(rows < 1 ? 1 : (rows > MAX_LONG_BLOCKS ? MAX_LONG_BLOCKS : rows));
+    return check_workspace(who, ws, ws_bytes, pl->bytes, 8, ANERF_EINVAL, "anerf_mesh_simplify_workspace");
 }
 
 }  // namespace
@@ -485,7 +392,6 @@ int anerf_mesh_simplify_count(const float* vertices, int64_t n_vertices, const i
     int *flag = at<int>(ws, pl.flag), *idx = at<int>(ws, pl.idx);
     long long* sums = at<long long>(ws, pl.sums);
     unsigned long long* keys = at<unsigned long long>(ws, pl.keys);
-    void* rows_ws = at<char>(ws, pl.rows_at);
     hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(cells)), dim3(NTHR), 0, s, table, cells, n_long);
     if (nv > 0) {
         hipLaunchKernelGGL(key_kernel, dim3(blocks_for(nv)), dim3(NTHR), 0, s, vertices, nv, g, table, sums, cnt,
@@ -496,12 +402,7 @@ int anerf_mesh_simplify_count(const float* vertices, int64_t n_vertices, const i
     if (nv > 0 && nt > 0) {
         hipLaunchKernelGGL(owner_count_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv,
                            (const int*)rep, row_cnt);
-        hipLaunchKernelGGL(rows_count_kernel, dim3(pl.rows.nblocks), dim3(NTHR), 0, s, (const int*)row_cnt, nv,
-                           pl.rows.counts(rows_ws), pl.rows.nblocks);
-        scan_block_sums(pl.rows, rows_ws, at<int64_t>(ws, pl.row_total), s);
-        hipLaunchKernelGGL(rows_offsets_kernel, dim3(pl.rows.nblocks), dim3(NTHR), 0, s, (const int*)row_cnt, nv,
-                           (const long long*)rows_ws, (const long long*)at<long long>(ws, pl.row_total), row_off,
-                           long_list, n_long);
+        exclusive_scan<false, SHORT_ROW>(row_cnt, nv, row_off, at<int>(ws, pl.tiles), nullptr, long_list, n_long, s);
         hipLaunchKernelGGL(fill_rows_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, (const int*)rep,
                            row_cnt, (const int*)row_off, keys, idx);
     }
@@ -509,8 +410,8 @@ int anerf_mesh_simplify_count(const float* vertices, int64_t n_vertices, const i
         hipLaunchKernelGGL(dedup_kernel, dim3(blocks_for(nt)), dim3(NTHR), 0, s, triangles, nt, nv, (const int*)rep,
                            (const int*)row_off, (const unsigned long long*)keys, (const int*)idx, flag);
         if (nv > 0 && nt > SHORT_ROW)
-            hipLaunchKernelGGL(long_rows_kernel, dim3(long_blocks(nt)), dim3(NTHR), 0, s, (const int*)row_off, keys, idx,
-                               nv, nt, (const int*)long_list, (const int*)n_long, flag);
+            hipLaunchKernelGGL(long_rows_kernel, dim3(long_blocks(nt, SHORT_ROW)), dim3(NTHR), 0, s, (const int*)row_off,
+                               keys, idx, nv, nt, (const int*)long_list, (const int*)n_long, flag);
     }
     hipLaunchKernelGGL(out_count_kernel, dim3(pl.out.nblocks), dim3(NTHR), 0, s, (const int*)rep, (long long)nv,
                        (const int*)flag, nt, pl.out.counts(ws), pl.out.nblocks);

@@ -126,6 +126,18 @@ def wheel(n, period=None):
     return _ro(v)[0], tri
 
 
+@functools.lru_cache(maxsize=None)
+def wheels(case):
+    """(vertices, triangles) of _smooth_cases' WHEEL_SETS: wheel i at wheel()'s positions shifted by (0, 2 i, 0).  With
+    cell 1 from the origin nothing merges (every wheel has a row of cells of its own): hub i owns its wheel's
+    triangles, and the list comes back unchanged."""
+    ns = S.WHEEL_SETS[case]
+    v = np.concatenate([wheel(n)[0] + np.array([0, 2 * i, 0], F) for i, n in enumerate(ns)]).astype(F)
+    tri, nv = S.wheels(*ns)
+    assert len(v) == nv
+    return _ro(v)[0], tri
+
+
 def small(name, seed=3):
     """(vertices, triangles) of one of _mesh_cases' small synthetic lists, at fixed random positions."""
     tri, nv, _ = M.synthetic(name)

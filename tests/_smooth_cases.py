@@ -38,6 +38,24 @@ def wheel(n):
     return _ro(tri)[0], n + 1
 
 
+@functools.lru_cache(maxsize=None)
+def wheels(*ns):
+    """(triangles, V) of disjoint wheels of ns[0], ns[1], ... triangles in one list, wheel i's ids after wheel
+    i - 1's (wheels of 33: offset by 34 i)."""
+    parts, nv = [], 0
+    for n in ns:
+        tri, v = wheel(n)
+        parts.append(tri + nv)
+        nv += v
+    return _ro(np.concatenate(parts).astype(np.int32))[0], nv
+
+
+# many_wheels: 1100 wheels of 33, every hub's row just over SHORT_ROW (66 listed pairs) and more rows than the 1024
+# workgroups of the long-row kernels, so that 76 of them take a second row.  mixed_wheels: a short-of-LDS row, a row
+# sorted over LDS and a row sorted over global memory on one list.
+WHEEL_SETS = {"many_wheels": (33,) * 1100, "mixed_wheels": (33, 40, 5000)}
+
+
 def wheel_vertices(n, seed=11):
     """Positions for wheel(n): the hub above a noisy unit circle."""
     rng = np.random.default_rng(seed)
@@ -47,8 +65,8 @@ def wheel_vertices(n, seed=11):
 
 
 def triangle_list(case):
-    """(triangles, V) of a case: a named mesh, "name/kind" relabelled, "hemisphere", "wheel<n>", or one of
-    _mesh_cases' synthetic lists."""
+    """(triangles, V) of a case: a named mesh, "name/kind" relabelled, "hemisphere", "wheel<n>", one of WHEEL_SETS, or
+    one of _mesh_cases' synthetic lists."""
     if case in M.MESHES:
         v, t = M.mesh(case)
         return t, len(v)
@@ -57,6 +75,8 @@ def triangle_list(case):
     if case == "hemisphere":
         v, t = hemisphere()
         return t, len(v)
+    if case in WHEEL_SETS:
+        return wheels(*WHEEL_SETS[case])
     if case.startswith("wheel"):
         return wheel(int(case[5:]))
     return M.synthetic(case)[:2]

@@ -103,6 +103,26 @@ def test_a_long_row_of_copies():
     _assert_same(got, meshops.simplify_mesh_reference(v, t, 1.0, origin=(0, 0, 0)), "wheel of 5000 in 7 cells")
 
 
+def test_many_long_owner_rows():
+    """1100 hubs that own 33 triangles each, more than the 1024 workgroups of the long-row kernel: 76 of them sort a
+    second row.  Nothing merges."""
+    v, t = C.wheels("many_wheels")
+    assert (len(v), len(t)) == (37400, 36300)
+    got = _run(v, t, 1.0, (0, 0, 0))
+    np.testing.assert_array_equal(got.triangles.cpu().numpy(), t)
+    np.testing.assert_array_equal(got.vertex_map.cpu().numpy(), np.arange(37400))
+    _assert_same(got, meshops.simplify_mesh_reference(v, t, 1.0, origin=(0, 0, 0)), "many_wheels")
+
+
+def test_mixed_owner_rows():
+    """wheel33, wheel40 and wheel5000 in one list: two rows just over the switch and a far longer one on the same
+    list of long rows."""
+    v, t = C.wheels("mixed_wheels")
+    assert (len(v), len(t)) == (5076, 5073)
+    _assert_same(_run(v, t, 1.0, (0, 0, 0)), meshops.simplify_mesh_reference(v, t, 1.0, origin=(0, 0, 0)),
+                 "mixed_wheels")
+
+
 @pytest.mark.parametrize("name", ("no_triangles", "no_vertices", "one_triangle", "degenerate", "duplicated"))
 def test_small_lists(name):
     v, t = C.small(name)

@@ -80,6 +80,26 @@ def test_wheel_by_construction():
     assert not b[0] and b[1:].all()
 
 
+def test_adjacency_of_many_long_rows():
+    """1100 hubs of 66 listed pairs each, more than the 1024 workgroups of the long-row kernels: 76 of them sort and
+    emit a second row, over the same LDS."""
+    tri, nv = S.triangle_list("many_wheels")
+    assert (nv, len(tri)) == (37400, 36300)
+    adj = meshops.vertex_adjacency(_dev(tri), nv)
+    _assert_adjacency(adj, S.adjacency("many_wheels"), "many_wheels")
+    off = adj.offsets.cpu().numpy()
+    assert off[-1] == 145200 and np.diff(off).max() == 33  # by construction: 33 + 33 x 3 per wheel
+    assert int(adj.boundary.sum()) == 36300  # every rim vertex, no hub
+
+
+def test_adjacency_of_mixed_long_rows():
+    """wheel33, wheel40 and wheel5000 in one list: rows sorted over LDS and a row sorted over global memory on the
+    same list of long rows."""
+    tri, nv = S.triangle_list("mixed_wheels")
+    assert (nv, len(tri)) == (5076, 5073)
+    _assert_adjacency(meshops.vertex_adjacency(_dev(tri), nv), S.adjacency("mixed_wheels"), "mixed_wheels")
+
+
 def test_adjacency_int64_and_host_input():
     tri, nv = S.triangle_list("blobs")
     ref = S.adjacency("blobs")

@@ -48,6 +48,19 @@ def test_checker_matches_the_brute_force_with_a_given_origin():
         _assert_same(C.reference("blobs", 2.0, origin)[:4], C.brute_force(v, t, 2.0, origin), f"blobs from {origin}")
 
 
+@pytest.mark.parametrize("case", sorted(C.S.WHEEL_SETS))
+def test_checker_on_disjoint_wheels(case):
+    """Nothing merges: the checker returns the list as it is, and agrees with the brute force on the smaller case."""
+    v, t = C.wheels(case)
+    assert (len(v), len(t)) == {"many_wheels": (37400, 36300), "mixed_wheels": (5076, 5073)}[case]
+    ref = meshops.simplify_mesh_reference(v, t, 1.0, origin=(0, 0, 0))
+    np.testing.assert_array_equal(ref.triangles, t)
+    np.testing.assert_array_equal(ref.vertex_map, np.arange(len(v)))
+    np.testing.assert_array_equal(ref.representatives, np.arange(len(v)))
+    if case == "mixed_wheels":
+        _assert_same(ref[:4], C.brute_force(v, t, 1.0, (0, 0, 0)), case)
+
+
 def test_outputs_are_consistent():
     """What the contract says of the outputs, read off the checker's: the representative is its cell's smallest
     member, the new vertices keep the order of their representatives, the survivors that of the input."""

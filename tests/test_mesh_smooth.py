@@ -83,6 +83,24 @@ def test_adjacency_reference_on_the_wheel(n):
     assert not adj.boundary[0] and adj.boundary[1:].all()
 
 
+@pytest.mark.parametrize("case", sorted(S.WHEEL_SETS))
+def test_adjacency_reference_on_disjoint_wheels(case):
+    """Every wheel of the list has its own wheel's adjacency, at its id offset."""
+    ns = S.WHEEL_SETS[case]
+    tri, nv = S.triangle_list(case)
+    adj = S.adjacency(case)
+    assert (nv, len(tri)) == {"many_wheels": (37400, 36300), "mixed_wheels": (5076, 5073)}[case]
+    assert adj.offsets[-1] == 4 * sum(ns) and np.diff(adj.offsets).max() == max(ns)
+    assert int(adj.boundary.sum()) == sum(ns)  # every rim vertex, no hub
+    for n in sorted(set(ns)):  # (the first wheel of every size)
+        first = sum(m + 1 for m in ns[:ns.index(n)])
+        one = S.adjacency(f"wheel{n}")
+        b, e = adj.offsets[first], adj.offsets[first + n + 1]
+        np.testing.assert_array_equal(adj.offsets[first:first + n + 2] - b, one.offsets)
+        np.testing.assert_array_equal(adj.neighbors[b:e] - first, one.neighbors)
+        np.testing.assert_array_equal(adj.boundary[first:first + n + 1], one.boundary)
+
+
 # ------------------------------------------------------------------ smoothing
 @pytest.mark.parametrize("w", [0.5, -0.53])
 @pytest.mark.parametrize("case", ["sphere", "torus", "hemisphere"])
