@@ -18,6 +18,7 @@ bf16x6 and the backward in bf16x3; fp32 accumulation in all (`anerf_gemm.hip`). 
 built and a GPU present.
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -55,9 +56,14 @@ FUSED_SKIP = True
 # fused pass, anerf_mlp_backward_head; an A/B switch for tools/train_bench.py
 FUSED_HEAD = True
 # (round 6) the caller's stream waits for the weight-gradient side stream at the end of the whole backward (an
-# autograd engine callback) instead of at the end of the MLP's backward, when no parameter already holds a .grad to
-# accumulate into: layer 0's weight gradient then overlaps the encoder's and the poses' backward; an A/B switch for
-# tools/train_bench.py, never read from the environment
+# autograd engine callback) instead of at the end of the MLP's backward: layer 0's weight gradient then overlaps the
+# encoder's and the poses' backward.  Only where nothing can touch the late gradients (layer 0's weight and bias, the
+# skip layer's weight) on the caller's stream before that callback, which defer_wgrad_sync_ok decides per backward:
+# leaves without a .grad (the engine hands the tensors over uncopied: pinned for the installed torch by
+# test_deferred_sync_one_application_hands_the_gradients_over_uncopied), without tensor or post-accumulate hooks, and
+# this application the only one of its network in the graph (a network applied twice, as train.py's single_net
+# does, has its contributions summed by the engine as soon as the second node returns).  Anything else waits at the
+# end of the MLP's backward.  An A/B switch for tools/train_bench.py, never read from the environment
 DEFER_WGRAD_SYNC = True
 # (round 6, ABI 19) the forward of every trunk layer (layer 0 on the encoder features, the hidden layers, the skip
 # layer on [x | h]) and of feature_linear on the persistent kernel anerf_mlp_forward_layer instead of anerf_mlp_gemm:
@@ -77,6 +83,62 @@ def _side_stream(dev):
     if key not in _SIDE:
         _SIDE[key] = torch.cuda.Stream(device=dev)
     return _SIDE[key]
+
+
+# The _MLP applications whose backward has not run and whose graph is still alive, per late parameter:
+# id(parameter) -> (weak reference to it, weak references to its _Application objects)
+_APPLIED = {}
+
+
+class _Application:
+    """One _MLP application's entry on its late parameters (layer 0's weight and bias, the skip layer's weight), kept
+    on the autograd node from nerf_forward until its backward has run or its graph is freed.  `shared`: another
+    application of one of these parameters was pending at the same time, so a backward through both gives that
+    parameter two contributions, which the engine sums on the caller's stream when the second node returns.  The
+    mark stays for the application's life: the node whose backward runs last must not defer either."""
+    __slots__ = ("shared", "_keys", "__weakref__")
+
+    def __init__(self, late):
+        self.shared = False
+        self._keys = []
+        for p in late:
+            ent = _APPLIED.get(id(p))
+            if ent is None or ent[0]() is not p:  # (an id used again by another tensor)
+                ent = _APPLIED[id(p)] = (weakref.ref(p), [])
+            for r in ent[1]:
+                other = r()
+                if other is not None:
+                    other.shared = self.shared = True
+            ent[1].append(weakref.ref(self))
+            self._keys.append(id(p))
+
+    def release(self):
+        """Its backward has run (or its graph is gone): later applications of the parameters stand alone again."""
+        keys, self._keys = self._keys, []
+        for k in keys:
+            ent = _APPLIED.get(k)
+            if ent is not None:
+                ent[1][:] = [r for r in ent[1] if r() is not None and r() is not self]
+                if not ent[1]:
+                    del _APPLIED[k]
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:  # (interpreter shutdown: the module's globals may be gone)
+            pass
+
+
+def defer_wgrad_sync_ok(late, application):
+    """May the caller's stream leave the wait for the late parameters' side-stream gradients to the end of the whole
+    backward (DEFER_WGRAD_SYNC)?  Only if nothing can read, sum or copy those gradients on the caller's stream before
+    then: `application` (the _Application of this _MLP node; None when _MLP was applied without nerf_forward) is the
+    only pending one of its parameters, and every parameter is a leaf without a .grad to accumulate into (the engine
+    then takes the tensor as .grad, uncopied), without tensor hooks and without post-accumulate-grad hooks."""
+    if not late or application is None or application.shared:
+        return False
+    return all(p.is_leaf and p.grad is None and not p._backward_hooks
+               and not getattr(p, "_post_accumulate_grad_hooks", None) for p in late)
 
 
 def _seg(t, cols, off=0):
@@ -318,6 +380,10 @@ class _MLP(torch.autograd.Function):
 
         main = torch.cuda.current_stream(dev)
         side = _side_stream(dev) if WGRAD_OVERLAP else None
+        application = getattr(ctx, "application", None)
+        if application is not None:  # (read below; later applications of these parameters stand alone again)
+            ctx.application = None
+            application.release()
 
         def wg(n, k, dy, x, xt=()):
             """dW, db of one layer (x: its input segments over the tensors xt), on the side stream."""
@@ -484,12 +550,11 @@ class _MLP(torch.autograd.Function):
                 for t in (dwx, grads[2 * s1]):
                     t.record_stream(side)
             late = (params[0], params[1], params[2 * s1]) if dwx is not None else ()
-            if DEFER_WGRAD_SYNC and late and all(p.is_leaf and p.grad is None for p in late):
+            if DEFER_WGRAD_SYNC and defer_wgrad_sync_ok(late, application):
                 # layer 0's weight gradient (and the skip layer's x columns after it) are the last side-stream work:
                 # the caller's stream waits for everything before them now, and for them once the whole backward has
-                # been queued (the encoder's and the poses' backward run on meanwhile).  Their parameters are leaves
-                # without a .grad, so the engine hands the tensors over uncopied and no kernel reads them before that
-                # wait
+                # been queued (the encoder's and the poses' backward run on meanwhile).  defer_wgrad_sync_ok: the
+                # engine hands these tensors to .grad uncopied and unsummed, and no hook sees them before that wait
                 main.wait_event(ev_pre)
                 ev = torch.cuda.Event()
                 ev.record(side)
@@ -567,7 +632,10 @@ def nerf_forward(net, feat, codes=None, G=None):
     elif dnet % 4 or nv % 4 or feat.shape[1] % 4:
         feat, params, dnet, nv = _pad_to_segments(feat, params, W, D, skip, dnet, nv)
     shape = (W, D, skip, dnet, nv, fwd, bwd, nwin)
-    return _MLP.apply(shape, feat, codes, G, *params)
+    raw = _MLP.apply(shape, feat, codes, G, *params)
+    if raw.grad_fn is not None and skip >= 0:  # (the node is _MLP's ctx: what its backward reads)
+        raw.grad_fn.application = _Application((params[0], params[1], params[2 * (skip + 1)]))
+    return raw
 
 
 def _ceil4(x):

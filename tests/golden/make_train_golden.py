@@ -76,6 +76,11 @@ CONFIGS = {
     # LDS) and the full view columns both run against it; the fused hidden-layer backward at W 256
     "t14_nj65_d8w256": dict(H=256, NJ=65, S=32, I=16, D=8, W=256, tau=20.0, kind="rays", seed=48, n_rays=32,
                             n_poses=2),
+    # single_net + multires_views 0 at configs/surreal/surreal_single.txt's real width (8 x 256, skip 4): the one
+    # network is applied to the coarse and to the importance samples, so two _MLP nodes feed the same parameters
+    # where the fused backward, the merged layer-0 / skip-x weight gradient and its deferred side-stream wait apply
+    "t15_single_d8w256": dict(H=256, NJ=24, S=32, I=16, D=8, W=256, tau=20.0, kind="rays", seed=49, n_rays=32,
+                              n_poses=2, mrv=0, single=True),
 }
 FULL_LIMIT = 20000   # parameters with more entries are sampled
 SAMPLE = 4096

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import _wgrad_delay as wgrad_delay
+
 pytestmark = pytest.mark.gpu
 
 mlp = importlib.import_module("a-nerf_amd.mlp")
@@ -555,6 +557,128 @@ def test_deferred_side_stream_sync_gives_the_same_gradients(accumulate, monkeypa
     assert len(out[True]) == len(out[False]) > 10
     for a, b in zip(out[True], out[False]):
         assert torch.equal(a, b)
+
+
+def _rel(a, b):
+    return float((a.double().cpu() - b.double().cpu()).norm() / max(float(b.double().norm()), 1e-30))
+
+
+def _deferral_scenario(monkeypatch, scenario, napps, seed, decisions):
+    """One scenario of the deferred wait under a late side stream (tests/_wgrad_delay.py).  `scenario(net, f, f2, g,
+    g2)` runs the forward and backward passes of the 8 x 256 network `net` on the feature rows f [4000] and f2 [2000]
+    with the upstream gradients g, g2, and returns further tensors to compare (what its hooks saw).  Three runs on
+    fresh modules -- DEFER_WGRAD_SYNC on with the delay (first: no earlier run of this test has left the right
+    answer in memory the allocator hands out again; the warm-up that measures the scenario's time runs on other
+    upstream gradients, and the seed is the test's own), off with the delay, off without -- must give every parameter's
+    and the features' gradients bit for bit: the same kernels on the same inputs, only the waits differ.  Each run
+    took the merged layer-0 weight gradient `napps` times, and the first one's _MLP nodes decided `decisions` (True:
+    this node leaves its wait to the end of the whole backward), in backward order.  The last run is then held against the same train.NeRF on
+    torch's GEMMs in float64 on the CPU (mlp "fp32" on a .double() copy), at the bounds of
+    test_nerf_forward_backward_matches_fp32_module: relative Frobenius error <= 5e-3 per parameter, the feature
+    gradient's per-row relative error <= 1e-3 at the 99 % quantile."""
+    W = 256
+    cfg = anerf.RenderConfig(n_joints=24, netdepth=8, netwidth=W).validate()
+    ck = syn.make_checkpoint(seed, n_joints=24, D=8, W=W, fine=False)
+    gen = torch.Generator(device=DEV).manual_seed(1000 + seed)
+    rnd = lambda *s: torch.rand(*s, device=DEV, generator=gen)  # noqa: E731
+    feat, feat2 = rnd(4000, cfg.feature_dim) * 2 - 1, rnd(2000, cfg.feature_dim) * 2 - 1
+    gout, gout2, gwarm, gwarm2 = (torch.randn(m, 4, device=DEV, generator=gen) for m in (4000, 2000, 4000, 2000))
+    nets = []
+
+    def run(defer, cycles, g, g2):
+        monkeypatch.setattr(mlp, "DEFER_WGRAD_SYNC", defer)
+        calls, decided = wgrad_delay.patch_wgrad(monkeypatch, W, cycles), wgrad_delay.record_decisions(monkeypatch)
+        net = train.TrainRayCaster(cfg, ck, mlp="mixed").train().network_fn
+        nets.append(net)
+        f, f2 = feat.clone().requires_grad_(True), feat2.clone().requires_grad_(True)
+        extra, ms = wgrad_delay.timed_ms(lambda: scenario(net, f, f2, g, g2))
+        out = {"feat": f.grad.clone(), **({"feat2": f2.grad.clone()} if f2.grad is not None else {}),
+               **{k: p.grad.clone() for k, p in net.named_parameters()}, **{k: v.clone() for k, v in extra.items()}}
+        torch.cuda.synchronize()
+        assert calls[0] == napps, (calls[0], napps)
+        assert decided == (decisions if defer else []), (decided, decisions)
+        return out, ms
+
+    _, t_ms = run(False, 0, gwarm, gwarm2)  # (forward + backward: an upper bound of the backward's time)
+    cycles = wgrad_delay.delay_cycles(t_ms)
+    assert cycles > 0
+    on, off, plain = (run(d, c, gout, gout2)[0] for d, c in ((True, cycles), (False, cycles), (False, 0)))
+    assert set(on) == set(off) == set(plain) and len(plain) > 20
+    for k in plain:
+        assert not torch.isnan(plain[k]).any(), k
+        assert torch.equal(off[k], plain[k]), f"{k}: the immediate wait differs under the delay"
+        assert torch.equal(on[k], plain[k]), f"{k}: the deferred wait differs under the delay"
+    # the reference: the same module's torch form in float64 on the CPU
+    ref = train.NeRF(cfg).double()
+    ref.mlp = "fp32"
+    ref.load_state_dict({k: v.detach().double().cpu() for k, v in nets[-1].state_dict().items()})
+    c = lambda t: t.detach().double().cpu()  # noqa: E731
+    rf, rf2 = c(feat).requires_grad_(True), c(feat2).requires_grad_(True)
+    rextra = scenario(ref, rf, rf2, c(gout), c(gout2))
+    want = {"feat": rf.grad, **({"feat2": rf2.grad} if rf2.grad is not None else {}),
+            **{k: p.grad for k, p in ref.named_parameters()}, **rextra}
+    assert set(want) == set(plain)
+    for k in plain:
+        if k in ("feat", "feat2"):
+            row = (c(plain[k]) - want[k]).norm(dim=1) / want[k].norm(dim=1).clamp_min(1e-30)
+            q99 = float(torch.quantile(row, 0.99))
+            print(f"{k}: per-row 99% {q99:.2e}, rel {_rel(plain[k], want[k]):.2e}")
+            assert q99 <= 1e-3, (k, q99)
+        else:
+            assert _rel(plain[k], want[k]) <= 5e-3, (k, _rel(plain[k], want[k]))
+    return plain
+
+
+def test_deferred_sync_one_application_hands_the_gradients_over_uncopied(monkeypatch):
+    """(a) The product's default two-network path: one application, no .grad yet.  The deferral holds only if the
+    engine takes the late gradients (views of the merged [dW_0 ; dW_s,x] and its bias) as .grad without a copy on
+    the caller's stream: a copy there would read the NaN the delayed side stream has not yet overwritten.  This
+    pins that for the installed torch."""
+    def scenario(net, f, f2, g, g2):
+        (net(f, None) * g).sum().backward()
+        return {}
+    _deferral_scenario(monkeypatch, scenario, 1, 11, [True])
+
+
+def test_deferred_sync_network_applied_twice_in_one_graph(monkeypatch):
+    """(b) One network applied twice in one graph (what train.py's single_net does, here without that flag: the
+    guard is the MLP's own, for any caller).  The engine sums the two nodes' contributions to layer 0 and the skip
+    layer's weight on the caller's stream as soon as the second node returns: neither node may defer."""
+    def scenario(net, f, f2, g, g2):
+        ((net(f, None) * g).sum() + (net(f2, None) * g2).sum()).backward()
+        return {}
+    _deferral_scenario(monkeypatch, scenario, 2, 12, [False, False])
+
+
+@pytest.mark.parametrize("hook", ["tensor_hook_on_layer0_weight", "post_accumulate_hook_on_skip_weight"])
+def test_deferred_sync_with_a_hook_on_a_late_parameter(hook, monkeypatch):
+    """(c) A hook on a late parameter runs on the caller's stream before the engine's callback: a tensor hook on
+    pts_linears[0].weight that clones the gradient it is handed, a post-accumulate-grad hook on the skip layer's weight
+    that clones .grad.  Each clone is the final gradient (and, with every other tensor, bit-identical across the
+    three runs)."""
+    def scenario(net, f, f2, g, g2):
+        seen = {}
+        if hook.startswith("tensor"):
+            p = net.pts_linears[0].weight
+            h = p.register_hook(lambda gr: seen.__setitem__("seen", gr.clone()))
+        else:
+            p = net.pts_linears[net.skips[0] + 1].weight
+            h = p.register_post_accumulate_grad_hook(lambda q: seen.__setitem__("seen", q.grad.clone()))
+        (net(f, None) * g).sum().backward()
+        h.remove()
+        assert torch.equal(seen["seen"], p.grad)
+        return seen
+    _deferral_scenario(monkeypatch, scenario, 1, 13 if hook.startswith("tensor") else 15, [False])
+
+
+def test_deferred_sync_second_backward_accumulates(monkeypatch):
+    """(d) A second backward into existing .grad tensors (the engine adds on the caller's stream: the MLP waits at
+    once), after a first that may defer, both under the delay."""
+    def scenario(net, f, f2, g, g2):
+        (net(f, None) * g).sum().backward()
+        (net(f2, None) * g2).sum().backward()
+        return {}
+    _deferral_scenario(monkeypatch, scenario, 2, 14, [True, False])
 
 
 def _backward_hidden(m, dy, x, w, lddx=None):

@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _wgrad_delay as wgrad_delay
 from _golden import Golden
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,8 @@ train = importlib.import_module("a-nerf_amd.train")
 
 TRAIN = ["t1_s32i16_d4w128", "t2_s64i16_d8w256", "t3_softplus_fc", "t4_tau200", "t5_single_mrv0",
          "t6_lindisp_raynoise", "t7_single_raynoise", "t8_freqsched", "t9_cutto_shift", "t10_cutoffbones",
-         "t11_mr5_mrv2_world", "t12_staged_relpos_rayangle_mrb2", "t13_querypts_shift", "t14_nj65_d8w256"]
+         "t11_mr5_mrv2_world", "t12_staged_relpos_rayangle_mrb2", "t13_querypts_shift", "t14_nj65_d8w256",
+         "t15_single_d8w256"]
 TOL = 1e-4
 TOL_ALPHA = 2e-3
 GRAD_REL = 2e-3
@@ -148,6 +150,46 @@ def test_fine_stream_is_bit_identical(name, monkeypatch):
         assert torch.equal(p1[k], p0[k]), k
     for k in q0:
         assert torch.equal(q1[k], q0[k]), k
+
+
+def test_shared_network_deferred_sync_is_bit_identical_under_a_delayed_wgrad(monkeypatch):
+    """single_net at 8 x 256 (t15): the one network runs on the coarse and on the importance samples, so two _MLP
+    nodes send gradients for layer 0 and the skip layer's weight to the same parameters, and the engine sums them on
+    the caller's stream when the second node returns.  With the merged layer-0 weight gradient made late on the side
+    stream (tests/_wgrad_delay.py: NaN fill, a bounded spin of three times the step's own time, then the kernel),
+    mlp.DEFER_WGRAD_SYNC on (the default, first) and off give the outputs, dL/dskts and every parameter gradient bit
+    for bit, and each step took the merged weight gradient twice."""
+    name = "t15_single_d8w256"
+    mlp = importlib.import_module("a-nerf_amd.mlp")
+    _, t_ms = wgrad_delay.timed_ms(lambda: _run(name))  # (the whole undelayed step: an upper bound of its backward)
+    cycles = wgrad_delay.delay_cycles(t_ms)
+    assert cycles > 0
+    res = {}
+    for defer in (True, False):
+        monkeypatch.setattr(mlp, "DEFER_WGRAD_SYNC", defer)
+        calls, decided = wgrad_delay.patch_wgrad(monkeypatch, 256, cycles), wgrad_delay.record_decisions(monkeypatch)
+        g, tr, sk, out, loss = _run(name)
+        assert g.cfg.single_net and tr.network_fine is tr.network_fn and calls[0] == 2, calls
+        assert decided == ([False, False] if defer else []), decided  # (neither node leaves its wait to the end)
+        res[defer] = ({k: v.detach().clone() for k, v in out.items()}, sk.grad.clone(),
+                      {k: p.grad.clone() for k, p in tr.named_parameters() if p.grad is not None})
+    (o1, s1, p1), (o0, s0, p0) = res[True], res[False]
+    for k in o0:
+        assert torch.equal(o1[k], o0[k]), k
+    assert not torch.isnan(s0).any() and torch.equal(s1, s0)
+    assert set(p1) == set(p0) and len(p0) > 20
+    for k in p0:
+        assert not torch.isnan(p0[k]).any(), k
+        assert torch.equal(p1[k], p0[k]), k
+
+
+def test_two_network_step_keeps_the_deferred_sync(monkeypatch):
+    """The default coarse + fine step at 8 x 256 (t2): each network is applied once, so both _MLP nodes leave the wait
+    for layer 0's weight gradient to the end of the whole backward (what mlp.DEFER_WGRAD_SYNC was measured for)."""
+    decided = wgrad_delay.record_decisions(monkeypatch)
+    g, tr, sk, out, loss = _run("t2_s64i16_d8w256")
+    assert not g.cfg.single_net and tr.network_fine is not tr.network_fn
+    assert decided == [True, True], decided
 
 
 def _run_again(g, tr):

@@ -4,6 +4,7 @@ core/networks/nerf.py:94-148, and state-dict key compatibility with the referenc
 import importlib
 
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -136,16 +137,83 @@ def test_checkpoint_is_tensors_and_round_trips(tmp_path):
         assert torch.equal(a, b), k
 
 
-def test_single_net_shares_one_module_and_fine_keys_win():
+@pytest.mark.parametrize("name", ["t5_single_mrv0", "t15_single_d8w256"])
+def test_single_net_shares_one_module_and_fine_keys_win(name):
     """single_net: network_fine IS network_fn (raycasters.py:98-104), both keys in the state dict;
     a checkpoint with two different nets loads network_fine's last (RayCaster.load_state_dict)."""
-    g = Golden("t5_single_mrv0")
+    g = Golden(name)
     tr = train.TrainRayCaster(g.cfg, g.ckpt, device="cpu")
     assert tr.network_fine is tr.network_fn
     ck = tr.checkpoint()
     assert set(ck["network_fn_state_dict"]) == set(ck["network_fine_state_dict"])
     for k, v in ck["network_fn_state_dict"].items():
         assert torch.equal(v, torch.as_tensor(g.ckpt["network_fine_state_dict"][k])), k
+
+
+def test_deferred_wgrad_sync_decision():
+    """mlp.defer_wgrad_sync_ok (with mlp._Application, what nerf_forward leaves on the _MLP node): the wait for the
+    late parameters' side-stream gradients may move to the end of the whole backward only when nothing reads, sums or
+    copies them on the caller's stream before: one pending application of the parameters, leaves, no .grad, no
+    hooks.  The GPU side is tests/test_gpu_mlp.py's test_deferred_sync_* and test_gpu_train.py's t15 test."""
+    mlp = importlib.import_module("a-nerf_amd.mlp")
+    ok, App = mlp.defer_wgrad_sync_ok, mlp._Application
+
+    def late():  # layer 0's weight and bias, the skip layer's weight
+        return tuple(torch.nn.Parameter(torch.zeros(s)) for s in ((4, 3), (4,), (4, 7)))
+    # the default two-network path: each network applied once per step; it defers, step after step
+    coarse, fine = late(), late()
+    for _ in range(2):
+        a, b = App(coarse), App(fine)
+        assert ok(coarse, a) and ok(fine, b)
+        a.release(), b.release()  # (their backward has run)
+    assert not mlp._APPLIED
+    # a graph dropped without a backward does not count against the next application
+    a = App(coarse)
+    del a
+    a = App(coarse)
+    assert ok(coarse, a)
+    a.release()
+    # one network applied twice in a graph: neither node defers -- the one whose backward runs last (the first
+    # applied) still has the sum ahead of it when the other's has run
+    a, b = App(coarse), App(coarse)
+    assert not ok(coarse, a) and not ok(coarse, b)
+    b.release()
+    assert not ok(coarse, a)
+    a.release()
+    a = App(coarse)  # (the next step stands alone again)
+    assert ok(coarse, a)
+    a.release()
+    # two applications that share one late parameter only
+    other = (coarse[0],) + late()[1:]
+    a, b = App(coarse), App(other)
+    assert not ok(coarse, a) and not ok(other, b)
+    a.release(), b.release()
+    assert not mlp._APPLIED
+    # _MLP applied without nerf_forward (no record of its applications), and a backward without late gradients
+    assert not ok(coarse, None)
+    assert not ok((), App(()))
+    # a tensor hook / a post-accumulate-grad hook on any late parameter; removed again: defers
+    for i, reg in ((0, "register_hook"), (2, "register_post_accumulate_grad_hook"), (1, "register_hook")):
+        h = getattr(coarse[i], reg)(lambda t: None)
+        a = App(coarse)
+        assert not ok(coarse, a)
+        h.remove()
+        assert ok(coarse, a)
+        a.release()
+    # a non-leaf (the zero-padded weights of joint counts that are no multiple of 4, mlp._pad_to_segments)
+    padded = (torch.cat([coarse[0], coarse[0].new_zeros(4, 1)], 1),) + coarse[1:]
+    a = App(padded)
+    assert not padded[0].is_leaf and not ok(padded, a)
+    a.release()
+    # a .grad to accumulate into, on any of the three
+    for i in range(3):
+        coarse[i].grad = torch.zeros_like(coarse[i])
+        a = App(coarse)
+        assert not ok(coarse, a)
+        coarse[i].grad = None
+        assert ok(coarse, a)
+        a.release()
+    assert not mlp._APPLIED
 
 
 def test_nerf_loss_functions_follow_trainer():

@@ -71,6 +71,10 @@ def parser():
     ap.add_argument("--no-defer-sync", action="store_true",
                     help="ablation: the caller's stream waits for the weight-gradient side stream at the end of the "
                          "MLP's backward (not at the end of the whole backward)")
+    ap.add_argument("--single-net", action="store_true",
+                    help="configs/surreal/surreal_single.txt's shape: one network for the coarse and the importance "
+                         "samples (two _MLP nodes on the same parameters: mlp.py waits for layer 0's weight gradient "
+                         "at the end of each MLP backward, whatever --no-defer-sync says)")
     ap.add_argument("--no-forward-persistent", action="store_true",
                     help="ablation: the hidden layers' forward on anerf_mlp_gemm instead of anerf_mlp_forward_hidden")
     ap.add_argument("--split-single", action="store_true",
@@ -93,7 +97,8 @@ def measure(a, dev=None):
                                                    for j in jobs]
     S, I, n = a.samples, a.importance, a.rays
     nj = getattr(a, "joints", 24)
-    cfg = anerf.RenderConfig(n_joints=nj, N_samples=S, N_importance=I).validate()
+    cfg = anerf.RenderConfig(n_joints=nj, N_samples=S, N_importance=I,
+                             single_net=bool(getattr(a, "single_net", False))).validate()
     ck = syn.make_checkpoint(13, n_joints=nj, D=8, W=256, fine=True, tau=20.0)
     sc = syn.make_scene(n_joints=nj, H=512, W=512, seed=13, n_frames=a.images, yaw_step=2 * np.pi / a.images)
     idx, cyls, _ = anerf.rays.valid_pixels(sc["c2ws"], 512, 512, sc["focal"], kps=sc["kps"], ext_scale=0.001)
