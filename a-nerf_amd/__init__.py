@@ -15,7 +15,8 @@ from .meshops import (filter_mesh, mesh_components, mesh_components_reference, m
                       vertex_normals, vertex_normals_reference, SimplifiedMesh, SIMPLIFY_MAX_CELLS, camera_view,
                       rasterize_mesh_camera, rasterize_mesh_camera_reference, render_mesh_views,
                       render_mesh_views_reference, MeshRaster, MeshViews)
-from . import dataset, rays, synthetic, train
+from . import dataset, rays, synthetic, train, trainer
+from .trainer import Adam, Trainer, create_popt, nerf_loss_reference, pose_loss_reference, adam_reference
 from .dataset import RayImageDataset, RayImageSampler
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
@@ -26,4 +27,5 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "vertex_normals_reference", "rasterize_mesh", "rasterize_mesh_reference", "mesh_turntable",
            "turntable_transforms", "simplify_mesh", "simplify_mesh_reference", "SimplifiedMesh",
            "SIMPLIFY_MAX_CELLS", "camera_view", "rasterize_mesh_camera", "rasterize_mesh_camera_reference",
-           "render_mesh_views", "render_mesh_views_reference", "MeshRaster", "MeshViews"]
+           "render_mesh_views", "render_mesh_views_reference", "MeshRaster", "MeshViews", "trainer", "Adam", "Trainer",
+           "create_popt", "nerf_loss_reference", "pose_loss_reference", "adam_reference"]

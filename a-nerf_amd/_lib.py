@@ -320,7 +320,40 @@ SIGNATURES = {
                                        ctypes.c_void_p,
                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                        ctypes.c_size_t, ctypes.c_void_p]),
+    "anerf_train_loss_workspace": (ctypes.c_size_t, [ctypes.c_int64]),
+    "anerf_train_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
+                                        ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "anerf_train_loss_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                                 ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32,
+                                                 ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p,
+                                                 ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "anerf_pose_loss_workspace": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
+    "anerf_pose_loss": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p]),
+    "anerf_pose_loss_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "anerf_adam_step_workspace": (ctypes.c_size_t, [c_i64p, ctypes.c_int32]),
+    "anerf_adam_step": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), c_i64p,
+                                       ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p]),
 }
+ANERF_LOSS_KINDS = {"MSE": 0, "L1": 1, "Huber": 2}  # include/anerf.h ANERF_LOSS_*
+ANERF_REG_NONE, ANERF_REG_BCE = 0, 1
 
 _lib = None
 

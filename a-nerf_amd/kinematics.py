@@ -226,27 +226,34 @@ class PoseOptLayer(torch.nn.Module):
             return self.rest_pose[torch.as_tensor(np.asarray(rest_pose_idxs), device=self.device)]
         return self.rest_pose[torch.as_tensor(self.rest_pose_idxs[np.asarray(kp_idxs)], device=self.device)]
 
+    def all_frames(self):
+        """Every frame's (kp, bone, skts, l2ws, rots) from one chain evaluation, differentiable: what
+        calculate_kinematic gathers a device batch from, and what the Trainer's temporal loss gathers the batch and
+        both of its neighbours from."""
+        if self.kp_map is None:
+            pelvis, bone = self.pelvis, self.bones
+        else:
+            pelvis = self.pelvis
+            bone = torch.cat([self.root_bones[:, None, :], self.bones[self.kp_map]], dim=1)
+        if len(self.rest_pose) == 1 or self.rest_pose_idxs is None:
+            ridx = None
+        else:
+            if getattr(self, "_ridx_all", None) is None or self._ridx_all.device != self.device:
+                self._ridx_all = torch.as_tensor(np.asarray(self.rest_pose_idxs), dtype=torch.int32,
+                                                 device=self.device)
+            ridx = self._ridx_all
+        o = pose_kinematics(bone, self.rest_pose, self.skel_type, pelvis=pelvis, rest_idx=ridx,
+                            device=self.device)
+        return o["kps"], bone, o["skts"], o["l2ws"], o["rots"]
+
     def calculate_kinematic(self, idxs, rest_pose_idxs=None):
         """-> kp (N, NJ, 3), bone (N, NJ, 3|6), skts (N, NJ, 4, 4), l2ws (N, NJ, 4, 4), rots (N, NJ, 3, 3).
         idxs: a host array (the reference's kp_idx) or a device tensor (a batch already on the device)."""
         if (isinstance(idxs, torch.Tensor) and idxs.device.type != "cpu" and rest_pose_idxs is None
                 and self.N_kps <= ALL_FRAMES_MAX):
             g = idxs.to(device=self.device, dtype=torch.long).reshape(-1)
-            if self.kp_map is None:
-                pelvis, bone = self.pelvis, self.bones
-            else:
-                pelvis = self.pelvis
-                bone = torch.cat([self.root_bones[:, None, :], self.bones[self.kp_map]], dim=1)
-            if len(self.rest_pose) == 1 or self.rest_pose_idxs is None:
-                ridx = None
-            else:
-                if getattr(self, "_ridx_all", None) is None or self._ridx_all.device != self.device:
-                    self._ridx_all = torch.as_tensor(np.asarray(self.rest_pose_idxs), dtype=torch.int32,
-                                                     device=self.device)
-                ridx = self._ridx_all
-            o = pose_kinematics(bone, self.rest_pose, self.skel_type, pelvis=pelvis, rest_idx=ridx,
-                                device=self.device)
-            return o["kps"][g], bone[g], o["skts"][g], o["l2ws"][g], o["rots"][g]
+            kps, bone, skts, l2ws, rots = self.all_frames()
+            return kps[g], bone[g], skts[g], l2ws[g], rots[g]
         if isinstance(idxs, torch.Tensor):
             idxs = idxs.detach().cpu().numpy()
         if idxs is None:

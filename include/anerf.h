@@ -68,6 +68,10 @@
  *   anerf_mlp_forward_layer    the same for any 256-output layer: layer 0, the skip layer, the heads (ABI 19)
  *   anerf_mlp_gemm_persistent  the same kernel as a product of any width (the feature gradient, ABI 19)
  *   anerf_mlp_forward(_pack)  the whole forward in one kernel (opt-in alternative to the GEMMs)
+ * The tail of a training step (Trainer.compute_loss / optimize):
+ *   anerf_train_loss (+ _backward)   Trainer._compute_nerf_loss, fine and coarse    core/trainer.py:353-380
+ *   anerf_pose_loss (+ _backward)    Trainer._compute_kp_loss                        core/trainer.py:382-441
+ *   anerf_adam_step         torch.optim.Adam's update over a table of tensors + get_gradnorm   core/trainer.py:191-203
  */
 #ifndef ANERF_H
 #define ANERF_H
@@ -981,6 +985,79 @@ int anerf_mlp_forward_layer(int64_t m, int32_t k, const anerf_seg* a, int32_t n_
  * n = the encoder columns). */
 int anerf_mlp_gemm_persistent(int64_t m, int32_t n, int32_t k, const anerf_seg* a, int32_t n_a, const void* b_split,
                               int32_t precision, const float* bias, int32_t relu, float* c, int64_t ldc, void* stream);
+
+/* ---- The tail of a training step (anerf_step.hip; new entries, no struct: ABI 26 still) --------------------------
+ * Trainer.compute_loss / optimize (core/trainer.py:319-483) as short fixed launch sequences that never wait for the
+ * host.  Every sum has a fixed shape (per workgroup, then one workgroup over the partials in index order, in double):
+ * two calls give the same bits; no atomics.  All pointers are device pointers unless said otherwise. */
+#define ANERF_LOSS_MSE 0   /* img2mse */
+#define ANERF_LOSS_L1 1    /* img2l1 */
+#define ANERF_LOSS_HUBER 2 /* F.smooth_l1_loss(beta) */
+#define ANERF_REG_NONE 0
+#define ANERF_REG_BCE 1    /* acc2bce(acc, fgs, reduction='off'): eps 1e-8, the mean over fgs < 1 */
+
+/* Workspace bytes of anerf_train_loss for n rays (0: refused, see anerf_last_error). */
+size_t anerf_train_loss_workspace(int64_t n);
+/* Trainer._compute_nerf_loss (core/trainer.py:353-380) of the fine outputs rgb [n][3], acc [n] and, unless both are
+ * NULL, the coarse outputs rgb0, acc0, against target [n][3]:  pred = rgb + (1 - acc) bg when use_background (bg =
+ * bgs [n][3], or base_bg when bgs is NULL), loss = mean of the loss kind over pred - target (the coarse one times
+ * coarse_weight), the regulariser reg_coef * BCE(acc, fgs [n]) per pass (not coarse-weighted).
+ * out [8] = rgb_loss, rgb_loss0, reg_loss, reg_loss0, psnr, psnr0, alpha, total:  psnr = -10 ln(mse) / ln 10 of pred
+ * whatever the loss kind, alpha = mean(acc), total = the sum of the four losses; entries of an absent pass or
+ * regulariser are 0; no ray with fgs < 1: reg_loss is NaN, as torch's mean of nothing.
+ * The workspace (8-byte aligned) keeps the sums for anerf_train_loss_backward. */
+int anerf_train_loss(const float* rgb, const float* acc, const float* rgb0, const float* acc0, const float* target,
+                     const float* bgs, float base_bg, const float* fgs, int64_t n, int32_t loss_kind, float beta,
+                     int32_t use_background, float coarse_weight, int32_t reg_kind, float reg_coef, float* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Its gradient: g_rgb [n][3], g_acc [n] (g_rgb0, g_acc0 with the coarse pair) = upstream[0] * d total / d input, with
+ * the same arguments and the workspace of the forward call; upstream is a device scalar. */
+int anerf_train_loss_backward(const float* rgb, const float* acc, const float* rgb0, const float* acc0,
+                              const float* target, const float* bgs, float base_bg, const float* fgs, int64_t n,
+                              int32_t loss_kind, float beta, int32_t use_background, float coarse_weight,
+                              int32_t reg_kind, float reg_coef, const void* workspace, size_t workspace_bytes,
+                              const float* upstream, float* g_rgb, float* g_acc, float* g_rgb0, float* g_acc0,
+                              void* stream);
+
+/* Workspace bytes of anerf_pose_loss (0: refused). */
+size_t anerf_pose_loss_workspace(int64_t n, int32_t n_joints);
+/* Trainer._compute_kp_loss (core/trainer.py:382-441).  cur: the per-ray rotations [n][NJ][3][3] when rot6d (the
+ * [:3, :2] block is read, six values in row-major order) or the axis-angle bones [n][NJ][3]; anchor [n_poses][NJ][6 | 3]
+ * and anchor_kps [n_poses][NJ][3] are gathered at kp_idx [n] (int64; an index outside [0, n_poses) reads nothing and
+ * makes the losses NaN); kps [n][NJ][3].
+ *   kp_loss   = coef * mean over n (NJ - 1) of sum_c max(d - tol, 0) where d = (anchor - cur)^2 > tol, joint 0 excluded
+ *   temp_loss = temp_coef * mean over n NJ of (|2 cur - prev_cur - next_cur|^2 + |2 kps - prev_kps - next_kps|^2)
+ *               * temp_val[n], with prev / next (constants, laid out as cur and kps) and temp_val all given or all NULL
+ *   MPJPC     = mean |anchor_kps[kp_idx] - kps| / ext_scale (no gradient)
+ * out [4] = kp_loss, temp_loss, MPJPC, kp_loss + temp_loss. */
+int anerf_pose_loss(const float* cur, int32_t rot6d, const float* anchor, const int64_t* kp_idx, int64_t n,
+                    int32_t n_joints, int64_t n_poses, const float* kps, const float* anchor_kps,
+                    const float* prev_cur, const float* next_cur, const float* prev_kps, const float* next_kps,
+                    const float* temp_val, float tol, float coef, float temp_coef, float ext_scale, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* Its gradient times upstream[0] (a device scalar): g_cur in cur's layout (rot6d: the third column 0) and, with the
+ * temporal term, g_kps [n][NJ][3] (otherwise g_kps may be NULL; given, it is zero-filled). */
+int anerf_pose_loss_backward(const float* cur, int32_t rot6d, const float* anchor, const int64_t* kp_idx, int64_t n,
+                             int32_t n_joints, int64_t n_poses, const float* kps, const float* prev_cur,
+                             const float* next_cur, const float* prev_kps, const float* next_kps,
+                             const float* temp_val, float tol, float coef, float temp_coef, const float* upstream,
+                             float* g_cur, float* g_kps, void* stream);
+
+/* Workspace bytes of anerf_adam_step over tensors of numel[count] elements (HOST array; 0: refused): one double per
+ * chunk of 2048 elements of each tensor. */
+size_t anerf_adam_step_workspace(const int64_t* numel, int32_t count);
+/* torch.optim.Adam's update (betas, eps, weight_decay as L2; no amsgrad, no maximize) of `count` fp32 tensors given
+ * as HOST arrays of device pointers (params, grads, exp_avg, exp_avg_sq) and sizes: update number `step` (>= 1) at
+ * learning rate lr, in torch's operation order; any count (64 tensors per launch).  Tensors need 4-byte alignment
+ * only (a gradient may be a view); 16-byte aligned ones are read as float4.
+ * The same pass writes each chunk's sum of squared gradients to workspace[chunk_base ...] (doubles); with norms [2]
+ * (device) a last launch sums chunks [0, chunk_base + this call's) in index order and writes get_gradnorm's
+ * (core/trainer.py:191-203) total_norm = sqrt(sum) and avg_norm = sqrt(sum / norm_tensors).  Several calls (tensors
+ * at different update numbers) share a workspace through chunk_base; the last passes norms. */
+int anerf_adam_step(void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq,
+                    const int64_t* numel, int32_t count, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, int64_t step, int64_t chunk_base, int32_t norm_tensors, float* norms,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
