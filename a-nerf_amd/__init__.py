@@ -18,6 +18,9 @@ from .meshops import (filter_mesh, mesh_components, mesh_components_reference, m
 from . import dataset, rays, synthetic, train, trainer
 from .trainer import Adam, Trainer, create_popt, nerf_loss_reference, pose_loss_reference, adam_reference
 from .dataset import RayImageDataset, RayImageSampler
+from . import evaluation
+from .evaluation import (EvalScores, evaluate_box_metric, evaluate_frames, evaluate_frames_reference, evaluate_metric,
+                         render_testset)
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
@@ -28,4 +31,5 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "turntable_transforms", "simplify_mesh", "simplify_mesh_reference", "SimplifiedMesh",
            "SIMPLIFY_MAX_CELLS", "camera_view", "rasterize_mesh_camera", "rasterize_mesh_camera_reference",
            "render_mesh_views", "render_mesh_views_reference", "MeshRaster", "MeshViews", "trainer", "Adam", "Trainer",
-           "create_popt", "nerf_loss_reference", "pose_loss_reference", "adam_reference"]
+           "create_popt", "nerf_loss_reference", "pose_loss_reference", "adam_reference", "evaluation", "EvalScores",
+           "evaluate_frames", "evaluate_frames_reference", "evaluate_metric", "evaluate_box_metric", "render_testset"]

@@ -351,7 +351,13 @@ SIGNATURES = {
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                        ctypes.c_void_p]),
+    "anerf_eval_workspace": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "anerf_eval_frames": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, c_i32p,
+                                         c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p]),
 }
+ANERF_EVAL_BORDERS = {"same": 0, "valid": 1}  # include/anerf.h ANERF_EVAL_*
 ANERF_LOSS_KINDS = {"MSE": 0, "L1": 1, "Huber": 2}  # include/anerf.h ANERF_LOSS_*
 ANERF_REG_NONE, ANERF_REG_BCE = 0, 1
 

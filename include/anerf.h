@@ -1059,6 +1059,36 @@ int anerf_adam_step(void* const* params, const void* const* grads, void* const* 
                     double weight_decay, int64_t step, int64_t chunk_base, int32_t norm_tensors, float* norms,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Scoring rendered frames (anerf_eval.hip; new entries, no struct: ABI 26 still) ------------------------------
+ * PSNR's squared error and SSIM of F frames of one size H x W where they lie, for evaluate_metric
+ * (core/utils/evaluation_helpers.py:257-385) and run_render.py:883-968's scores inside a box.
+ * SSIM is Wang et al.'s, per channel: an 11-tap Gaussian window (sigma 1.5, normalised to sum 1) applied separably,
+ * K1 = 0.01, K2 = 0.03, C1 = (K1 data_range)^2, C2 = (K2 data_range)^2, mu = E[.], var = E[.^2] - mu^2,
+ *   map = ((2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1)) * ((2 cov_xy + C2) / (var_x + var_y + C2)),
+ * with moments, map and sums in double (the inputs widen exactly). */
+#define ANERF_EVAL_SAME 0  /* zeros outside the rectangle, weights not renormalised (a conv2d with padding 5) */
+#define ANERF_EVAL_VALID 1 /* the scored pixels lose 5 per side of the rectangle: windows that lie inside it only */
+
+/* Workspace bytes of anerf_eval_frames: nine doubles per frame and 32 x 16 tile (0: refused, see anerf_last_error). */
+size_t anerf_eval_workspace(int32_t n_frames, int32_t H, int32_t W);
+/* pred [F][H][W][3] fp32; gt the same, or bytes when gt_uint8 (a byte v is the fp32 that v / 255. rounds to); mask
+ * [F][H][W] bytes (nonzero = 1) or NULL (all ones).  rects and boxes are HOST arrays [F][4] of x0, y0, x1, y1 with
+ * exclusive upper bounds: a frame's rectangle is what the SSIM filter takes as the image (everything outside it is 0
+ * to the filter and is not scored; an empty one is legal and gives zero sums), its box a second, rectangular weight
+ * (boxes NULL: all ones).
+ *   sums [F][9] (device, double) = { n, sum se, sum ssim } over the scored pixels, over those with the mask set, over
+ *   those inside the box: n counts pixels, se = (gt - pred)^2 and ssim are summed over the 3 channels.
+ *   map [F][H][W][3] (device, may be NULL): the SSIM map rounded to fp32, 0 at every pixel that is not scored.
+ * Each workgroup writes its tile's nine sums to its own workspace slot and a last workgroup per frame adds the
+ * frame's slots in tile order: no atomics, the same bits on every run and whatever other frames are in the call.
+ * Allocation-free, asynchronous on `stream`, no host read (64 frames per launch).  ANERF_EINVAL, before any launch,
+ * for a NULL pred, gt, rects, sums or workspace, a negative size, H or W above 32768, a rectangle or box that is not
+ * 0 <= x0 <= x1 <= W, 0 <= y0 <= y1 <= H, an unknown border, data_range <= 0, a workspace not 8-byte aligned;
+ * ANERF_EWORKSPACE for a workspace that is too small. */
+int anerf_eval_frames(const float* pred, const void* gt, int32_t gt_uint8, const uint8_t* mask, const int32_t* rects,
+                      const int32_t* boxes, int32_t n_frames, int32_t H, int32_t W, double data_range, int32_t border,
+                      float* map, double* sums, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
