@@ -21,6 +21,11 @@ from .dataset import RayImageDataset, RayImageSampler
 from . import evaluation
 from .evaluation import (EvalScores, evaluate_box_metric, evaluate_frames, evaluate_frames_reference, evaluate_metric,
                          render_testset)
+from . import sequences
+from .sequences import (RenderSequence, load_animate, load_bubble, load_bullettime, load_correction,
+                        load_interpolate, load_pose_rotate, load_retarget, load_selected, matrix_to_axis_angle,
+                        matrix_to_axis_angle_reference, pose_ckpt_to_pose_data, pose_sequence,
+                        pose_sequence_reference, render_sequence, write_png)
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
@@ -32,4 +37,8 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "SIMPLIFY_MAX_CELLS", "camera_view", "rasterize_mesh_camera", "rasterize_mesh_camera_reference",
            "render_mesh_views", "render_mesh_views_reference", "MeshRaster", "MeshViews", "trainer", "Adam", "Trainer",
            "create_popt", "nerf_loss_reference", "pose_loss_reference", "adam_reference", "evaluation", "EvalScores",
-           "evaluate_frames", "evaluate_frames_reference", "evaluate_metric", "evaluate_box_metric", "render_testset"]
+           "evaluate_frames", "evaluate_frames_reference", "evaluate_metric", "evaluate_box_metric", "render_testset",
+           "sequences", "RenderSequence", "pose_sequence", "pose_sequence_reference", "render_sequence", "write_png",
+           "matrix_to_axis_angle", "matrix_to_axis_angle_reference", "pose_ckpt_to_pose_data", "load_retarget",
+           "load_bullettime", "load_pose_rotate", "load_interpolate", "load_animate", "load_bubble", "load_selected",
+           "load_correction"]

@@ -356,7 +356,16 @@ SIGNATURES = {
                                          c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_void_p]),
+    "anerf_rotation_to_axis_angle": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                                    ctypes.c_void_p]),
+    "anerf_sequence_bones": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_int32, c_i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
+                                            ctypes.c_int32, ctypes.c_int32, c_f, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
 }
+ANERF_SEQ_INTERPS = {"linear": 0, "slerp": 1}  # include/anerf.h ANERF_SEQ_*
+ANERF_SEQ_ROOT_KEEP, ANERF_SEQ_ROOT_CONST, ANERF_SEQ_ROOT_COMPOSE = 0, 1, 2
 ANERF_EVAL_BORDERS = {"same": 0, "valid": 1}  # include/anerf.h ANERF_EVAL_*
 ANERF_LOSS_KINDS = {"MSE": 0, "L1": 1, "Huber": 2}  # include/anerf.h ANERF_LOSS_*
 ANERF_REG_NONE, ANERF_REG_BCE = 0, 1

@@ -166,6 +166,29 @@ def get_smpl_l2ws(pose, rest_pose=None, scale=1.0, skel_type=SMPLSkeleton):
     return o["l2ws"][0] if single else o["l2ws"]
 
 
+@torch.no_grad()
+def matrix_to_axis_angle(R, device=None):
+    """Rotation matrices (..., 3, 3) or 6-D parameters (..., 6) -> axis-angle (..., 3), a float32 device tensor:
+    pytorch3d's matrix_to_axis_angle (skeleton_utils.py:405-418 rot_to_axisang / rot6d_to_axisang) on the device,
+    `anerf_rotation_to_axis_angle`: the inverse of the chain's axis-angle branch, angle in [0, pi], float64 inside."""
+    if device is None:
+        device = R.device if isinstance(R, torch.Tensor) and R.is_cuda else torch.device("cuda", 0)
+    r = _dev_f32(R, device)
+    if r.dim() >= 2 and tuple(r.shape[-2:]) == (3, 3):
+        lead, rot_dim = tuple(r.shape[:-2]), 9
+    elif r.dim() >= 1 and r.shape[-1] == 6:
+        lead, rot_dim = tuple(r.shape[:-1]), 6
+    else:
+        raise ValueError("matrix_to_axis_angle takes (..., 3, 3) matrices or (..., 6) parameters")
+    n = int(np.prod(lead, dtype=np.int64))
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        rc = _lib.load().anerf_rotation_to_axis_angle(_lib.ptr(r), rot_dim, n, _lib.ptr(out),
+                                                      _lib.stream_handle(device))
+    _lib.check(rc, "anerf_rotation_to_axis_angle")
+    return out
+
+
 class PoseOptLayer(torch.nn.Module):
     """The reference's PoseOptLayer (core/pose_opt.py:240-445) on the device, trainable: `pelvis`
     (N, 3) and `bones` (N, NJ, 3|6) — with kp_map, `root_bones` (N, 3|6) and the shared per-view
@@ -287,6 +310,8 @@ class PoseOptLayer(torch.nn.Module):
         return self.cache_kps[i], self.cache_bones[i], self.cache_skts[i], self.cache_l2ws[i], self.cache_rots[i]
 
     def get_bones(self, idx=None):
+        """pose_opt.py:343-350: the bones as axis-angle (6-D parameters through rot6d_to_axisang, on the device)."""
+        bones = self.idx_to_params(np.arange(self.N_kps) if idx is None else idx)[1]
         if self.use_rot6d:
-            raise NotImplementedError("get_bones with use_rot6d needs matrix_to_axis_angle (not on this path)")
-        return self.idx_to_params(np.arange(self.N_kps) if idx is None else idx)[1]
+            return matrix_to_axis_angle(bones, device=self.device)
+        return bones

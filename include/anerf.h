@@ -1089,6 +1089,46 @@ int anerf_eval_frames(const float* pred, const void* gt, int32_t gt_uint8, const
                       const int32_t* boxes, int32_t n_frames, int32_t H, int32_t W, double data_range, int32_t border,
                       float* map, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Pose sequences and the inverse rotation map (anerf_sequence.hip; new entries, no struct: ABI 26 still) -------
+ * The bones of run_render.py's render types (lines 484-865) for F output frames from K key poses, in one launch, and
+ * matrix -> axis-angle, the inverse of anerf_pose_kinematics' axis-angle branch.  Arithmetic in double, outputs
+ * rounded once to float; a thread per output element, no LDS and no atomics, the same bits on every run. */
+
+/* rots [n][9] (row-major 3x3) or [n][6] (rot6d_to_rotmat's parameters, applied first as anerf_pose_kinematics does)
+ * -> axisang_out [n][3]: pytorch3d's matrix_to_axis_angle.  The quaternion comes from the best conditioned of the
+ * four candidates, is normalised (the input may be orthogonal only to float rounding) and gets a real part >= 0, so
+ * the angle lies in [0, pi]; the axis-angle uses sin(half) / angle with the series 0.5 - angle^2 / 48 below 1e-6,
+ * as the forward map.  Finite at the identity, at angles of 1e-8 and next to pi (where the sign of the axis is free).
+ * Asynchronous on `stream`.  ANERF_EINVAL, before any launch, for another rot_dim, n outside [0, 2^40) or a NULL
+ * pointer with n > 0. */
+int anerf_rotation_to_axis_angle(const float* rots, int32_t rot_dim, int64_t n, float* axisang_out, void* stream);
+
+#define ANERF_SEQ_LINEAR 0 /* the reference's lerp of axis-angle vectors, a (1 - w) + b w */
+#define ANERF_SEQ_SLERP 1  /* per joint: axis-angle -> quaternion -> slerp along the shorter arc -> axis-angle */
+#define ANERF_SEQ_ROOT_KEEP 0
+#define ANERF_SEQ_ROOT_CONST 1   /* every key's root bone reads as root_const[3] (undo_rot: 1.5708, 0, 0) */
+#define ANERF_SEQ_ROOT_COMPOSE 2 /* root = axis-angle of rotate_{x,y,z}(angle_f) R(root): load_pose_rotate */
+
+/* key_bones [K][NJ][3] axis-angle and key_root [K][3] (device) -> bones_out [F][NJ][3], pelvis_out [F][3] (device).
+ * A frame's row of frame_keys [F][5] holds its first key, its second key, its base key, its pelvis key and the id of
+ * its root-rotation axis (0 x, 1 y, 2 z: skeleton_utils.py's rotate_x / _y / _z); its row of frame_vals [F][2] the
+ * weight w of the second key (the double of np.linspace(0, 1, n_step, endpoint=False)) and the root-rotation angle.
+ * Both tables are given twice, on the host (checked here: every key in [0, K), the axis id in [0, 2] under
+ * ANERF_SEQ_ROOT_COMPOSE, finite values) and on the device (read by the kernel; the caller uploads them once).
+ *   bone j of frame f = interp(key first, key second; w)  where joint_mask[j] != 0 (host [NJ]; NULL: every joint),
+ *                     = key base                            elsewhere (load_animate's joints),
+ *   pelvis of frame f = key_root[pelvis key].
+ * ANERF_SEQ_SLERP falls back to lerp-and-normalise of the quaternions when their dot product exceeds 1 - 1e-12
+ * (equal keys), and returns the rotation's angle in [0, pi].  The root bone (root_id) follows root_mode.
+ * Allocation-free, asynchronous on `stream`.  ANERF_EINVAL, before any launch, for a NULL pointer, K < 1, NJ outside
+ * [1, 128], root_id outside [0, NJ), F < 1 or F NJ > 2^31, an unknown interp or root_mode, ANERF_SEQ_ROOT_CONST
+ * without root_const (host [3]), or a table entry as above: the kernel never sees an index out of range. */
+int anerf_sequence_bones(const float* key_bones, const float* key_root, int32_t n_keys, int32_t n_joints,
+                         int32_t root_id, const int32_t* frame_keys_host, const double* frame_vals_host,
+                         const int32_t* frame_keys, const double* frame_vals, const uint8_t* joint_mask,
+                         int64_t n_frames, int32_t interp, int32_t root_mode, const float* root_const,
+                         float* bones_out, float* pelvis_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
