@@ -666,15 +666,47 @@ int anerf_train_encode_backward(const anerf_model* m, const float* ray_batch, in
     return ANERF_OK;
 }
 
+// Dynamic LDS of train_composite_backward_kernel ([9][ns] floats; it also holds TRAIN_COMPOSITE_BWD_STATIC_LDS
+// static bytes).  The forward needs less ([7][ns]), so both entry points refuse a sample count whose BACKWARD launch
+// would not fit the default dynamic-LDS limit: a forward that succeeds has a backward that can run.
+static inline size_t train_composite_backward_lds(int64_t n_samples) { return (size_t)9 * n_samples * sizeof(float); }
+constexpr size_t TRAIN_COMPOSITE_BWD_STATIC_LDS = 4 * sizeof(float);  // (sc[4] of the backward kernel)
+constexpr size_t TRAIN_COMPOSITE_LDS_LIMIT = 64 * 1024;               // (no hipFuncSetAttribute: the default limit)
+
+constexpr int TRAIN_COMPOSITE_MAX_SAMPLES = 1024;                      // (one wave per ray, LDS-staged)
+
+// The two limits are checked in the order LDS, cap, so each is reachable; at the cap the backward fits with room.
+static int check_train_composite_samples(const char* who, int64_t n_rays, int32_t n_samples) {
+    static_assert((size_t)9 * TRAIN_COMPOSITE_MAX_SAMPLES * sizeof(float) + TRAIN_COMPOSITE_BWD_STATIC_LDS <=
+                      TRAIN_COMPOSITE_LDS_LIMIT,
+                  "the sample cap must leave the composite backward inside the dynamic LDS limit");
+    char msg[192];
+    if (n_rays > 0x7fffffff) {
+        snprintf(msg, sizeof msg, "%s: too many rays for one launch", who);
+        return fail(ANERF_EINVAL, msg);
+    }
+    if (train_composite_backward_lds(n_samples) + TRAIN_COMPOSITE_BWD_STATIC_LDS > TRAIN_COMPOSITE_LDS_LIMIT) {
+        snprintf(msg, sizeof msg, "%s: n_samples %d: the backward needs %zu bytes of LDS, more than %zu", who,
+                 (int)n_samples, train_composite_backward_lds(n_samples) + TRAIN_COMPOSITE_BWD_STATIC_LDS,
+                 TRAIN_COMPOSITE_LDS_LIMIT);
+        return fail(ANERF_EINVAL, msg);
+    }
+    if (n_samples > TRAIN_COMPOSITE_MAX_SAMPLES) {
+        snprintf(msg, sizeof msg, "%s: more than %d samples per ray", who, TRAIN_COMPOSITE_MAX_SAMPLES);
+        return fail(ANERF_EINVAL, msg);
+    }
+    return ANERF_OK;
+}
+
 int anerf_train_composite(const anerf_model* m, const float* raw, const float* z, const float* ray_batch,
                           int32_t ray_stride, int64_t n_rays, int32_t n_samples, const float* noise, float* rgb,
                           float* disp, float* acc, float* weights, float* alpha, float* trans, void* stream) {
     if (!m || !raw || !z || !ray_batch || ray_stride < 6 || n_rays < 0 || n_samples < 1 || !rgb || !disp || !acc ||
         !weights || !alpha || !trans)
         return fail(ANERF_EINVAL, "anerf_train_composite: bad arguments");
+    if (int rc = check_train_composite_samples("anerf_train_composite", n_rays, n_samples)) return rc;
     if (n_rays == 0) return ANERF_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (n_rays > 0x7fffffff || n_samples > 1024) return fail(ANERF_EINVAL, "anerf_train_composite: more than 1024 samples per ray");
     hipLaunchKernelGGL(train_composite_kernel, dim3((unsigned)n_rays), dim3(64), (size_t)7 * n_samples * sizeof(float),
                        st, m->md, raw, z, ray_batch, ray_stride, n_rays, n_samples, noise, rgb, disp, acc, weights,
                        alpha, trans);
@@ -690,12 +722,11 @@ int anerf_train_composite_backward(const anerf_model* m, const float* raw, const
     if (!m || !raw || !z || !ray_batch || ray_stride < 6 || n_rays < 0 || n_samples < 1 || !weights || !alpha ||
         !trans || !g_raw)
         return fail(ANERF_EINVAL, "anerf_train_composite_backward: bad arguments");
+    if (int rc = check_train_composite_samples("anerf_train_composite_backward", n_rays, n_samples)) return rc;
     if (n_rays == 0) return ANERF_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (n_rays > 0x7fffffff || n_samples > 1024)
-        return fail(ANERF_EINVAL, "anerf_train_composite_backward: more than 1024 samples per ray");
     hipLaunchKernelGGL(train_composite_backward_kernel, dim3((unsigned)n_rays), dim3(64),
-                       (size_t)9 * n_samples * sizeof(float), st, m->md, raw, z, ray_batch, ray_stride, n_rays,
+                       train_composite_backward_lds(n_samples), st, m->md, raw, z, ray_batch, ray_stride, n_rays,
                        n_samples, noise, weights, alpha, trans, g_rgb, g_disp, g_acc, g_weights, g_alpha, g_raw);
     HIP_TRY(hipGetLastError());
     return ANERF_OK;

@@ -50,7 +50,9 @@ __host__ __device__ inline FeatLayout feat_layout(const ModelDev& M) {
 __device__ __forceinline__ float ray_angle(float qx, float qy, float qz, float ex, float ey, float ez, float& cs) {
     const float dot = qx * ex + qy * ey + qz * ez;  // ((a * b).sum(-1): elementwise products, then the sum)
     cs = dot / (norm3(qx, qy, qz) * norm3(ex, ey, ez));
-    const float cl = fminf(fmaxf(cs, -1.0f + 1e-6f), 1.0f - 1e-6f);
+    // (torch.clamp keeps NaN; fminf / fmaxf return the other operand, which would turn the NaN row of an
+    // out-of-range pose index into a finite angle)
+    const float cl = cs != cs ? cs : fminf(fmaxf(cs, -1.0f + 1e-6f), 1.0f - 1e-6f);
     return acosf(cl) - 1.5707963267948966f;
 }
 
@@ -182,6 +184,7 @@ __global__ void train_encode_kernel(ModelDev M, const float* __restrict__ rb, in
     } else {  // out-of-range pose index: NaN features, no out-of-bounds read
         const float q = __int_as_float(0x7fc00000);
         r0 = r1 = r2 = f32x4{q, q, q, q};
+        px = py = pz = q;  // (querypts reads the world point alone: its columns are NaN too)
     }
     const float S[12] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3], r2[0], r2[1], r2[2], r2[3]};
     encode_joint(M, S, j, px, py, pz, ray[3], ray[4], ray[5], feat + idx * F);
@@ -649,7 +652,7 @@ __global__ __launch_bounds__(64) void train_composite_backward_kernel(
     const float* __restrict__ trans, const float* __restrict__ g_rgb, const float* __restrict__ g_disp,
     const float* __restrict__ g_acc, const float* __restrict__ g_w, const float* __restrict__ g_alpha,
     float* __restrict__ g_raw) {
-    extern __shared__ float cl[];  // [8][ns]: w, z, alpha, P, sigmoid(rgb) (3), G, then P R
+    extern __shared__ float cl[];  // [9][ns]: w, z, alpha, P, sigmoid(rgb) (3), G, P R
     __shared__ float sc[4];        // r, gd_r, den, ga
     const int64_t i = blockIdx.x;
     if (i >= n) return;

@@ -745,7 +745,9 @@ int anerf_train_encode_backward(const anerf_model* m, const float* ray_batch, in
 
 /* raw2outputs of raw [N][S][4] at z [N][S] with noise [N][S] (= randn * raw_noise_std * B, added to
  * raw_sigma / B; NULL: none): rgb [N][3], disp [N], acc [N], weights, alpha and the exclusive
- * transmittance trans [N][S] (kept for the backward).  S <= 1024 (one wave per ray, LDS-staged). */
+ * transmittance trans [N][S] (kept for the backward).  S <= 1024 (one wave per ray, LDS-staged), and no S whose
+ * BACKWARD would not fit the 64 KB of dynamic LDS (9 S floats): ANERF_EINVAL before any launch, so a forward that
+ * succeeds has a backward that can run. */
 int anerf_train_composite(const anerf_model* m, const float* raw, const float* z, const float* ray_batch,
                           int32_t ray_stride, int64_t n_rays, int32_t n_samples, const float* noise, float* rgb,
                           float* disp, float* acc, float* weights, float* alpha, float* trans, void* stream);

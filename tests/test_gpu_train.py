@@ -5,9 +5,15 @@ reference's torch.rand / torch.randn draws recorded and fed back here).
 Tolerances:
   * rgb_map / disp_map / acc_map (+ coarse): 1e-4 absolute (north star); per-sample alpha 2e-3
     (hazard H11, see test_gpu_parity.py); loss 1e-5 relative
-  * gradients (per-ray skeleton transforms, every network parameter): |g - g_ref| <= 2e-3 max|g_ref|
+  * gradients (per-ray skeleton transforms, every network parameter): |g - g_ref| <= GRAD_REL[mlp] max|g_ref|
     per tensor and the norm of sampled tensors within 1e-3 relative — fp32 sums of thousands of
-    sample terms in a different order (GEMM reductions, atomics over samples)
+    sample terms in a different order (GEMM reductions, atomics over samples).  GRAD_REL by MLP mode:
+    mixed / mixed16 (bf16x3 gradient GEMMs) 2e-3; the fp32-accurate modes what they achieve against the
+    reference goldens -- the largest per-tensor error over t1-t15 and both view layouts, times 4 (the
+    atomics' order differs between machines), rounded up to one digit: fp32 2.25e-5 (t11, fine
+    pts_linears.1.weight) -> 9e-5, bf16x6 1.74e-4 (t14, fine pts_linears.7.weight) -> 7e-4.  Every run prints its mode's measured maximum
+    (test_report_measured_gradient_errors prints the table).  The kernels between the MLP and these
+    tensors are held to float64 one by one in tests/test_gpu_train_stages.py.
 """
 import importlib
 
@@ -30,7 +36,8 @@ TRAIN = ["t1_s32i16_d4w128", "t2_s64i16_d8w256", "t3_softplus_fc", "t4_tau200", 
          "t15_single_d8w256"]
 TOL = 1e-4
 TOL_ALPHA = 2e-3
-GRAD_REL = 2e-3
+GRAD_REL = {"mixed": 2e-3, "mixed16": 2e-3, "fp32": 9e-5, "bf16x6": 7e-4}
+MEASURED = {}  # mode -> (largest |g - g_ref| / max |g_ref| seen, where)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -75,7 +82,7 @@ def _run(name, mlp="mixed", view_windows=True):
 # the training MLP on the hand-written split-bf16 GEMMs (mixed — the default —, mixed16 and bf16x6) and on
 # torch's fp32 GEMMs; the view-window layout (the default where it applies) and the full view columns
 @pytest.fixture(scope="module", params=[(n, mlp, vw) for n in TRAIN for mlp in ("mixed", "mixed16", "bf16x6", "fp32")
-                                        for vw in (True, False) if vw or mlp in ("mixed", "fp32")],
+                                        for vw in (True, False) if vw or mlp in ("mixed", "fp32", "bf16x6")],
                 ids=lambda p: f"{p[0]}-{p[1]}" + ("" if p[2] else "-fullview"))
 def run(request):
     return _run(*request.param)
@@ -92,22 +99,34 @@ def test_train_outputs_match_reference(run):
     assert abs(loss.item() - float(g["loss"])) <= 1e-5 * abs(float(g["loss"])), (loss.item(), float(g["loss"]))
 
 
-def _close(a, ref, what):
+def _close(a, ref, what, mlp):
     scale = float(np.abs(ref).max())
     d = float(np.abs(a - ref).max())
-    assert d <= GRAD_REL * scale + 1e-12, f"{what}: max |grad - ref| {d:.3e} vs max |ref| {scale:.3e}"
+    if scale > 0 and d / scale > MEASURED.get(mlp, (0.0, None))[0]:
+        MEASURED[mlp] = (d / scale, what)
+    assert d <= GRAD_REL[mlp] * scale + 1e-12, f"{what}: max |grad - ref| {d:.3e} vs max |ref| {scale:.3e}"
+
+
+def _print_measured(mlp):
+    m, where = MEASURED.get(mlp, (0.0, None))
+    print(f"[{mlp}] largest |grad - ref| / max |ref| so far {m:.3e} at {where} (bound {GRAD_REL[mlp]:.0e})")
 
 
 def test_train_pose_gradient_matches_reference(run):
     g, tr, sk, out, loss = run
     gs = sk.grad.detach().cpu().numpy()
-    _close(gs, g["grad_skts"], f"{g.name} dL/dskts")
+    mlp = tr.network_fn.mlp
+    try:
+        _close(gs, g["grad_skts"], f"{g.name} dL/dskts", mlp)
+    finally:
+        _print_measured(mlp)
     assert np.all(gs[:, :, 3, :] == 0.0)
 
 
 def test_train_parameter_gradients_match_reference(run):
     g, tr, sk, out, loss = run
     nets = {"fn": tr.network_fn, "fine": tr.network_fine}
+    mlp = tr.network_fn.mlp
     n_checked = 0
     for key in g.d:
         if not key.startswith("grad_") or key == "grad_skts" or key.endswith("__idx") or key.endswith("__norm"):
@@ -119,7 +138,10 @@ def test_train_parameter_gradients_match_reference(run):
             norm_ref = float(g[key + "__norm"])
             assert abs(np.linalg.norm(gp.astype(np.float64)) - norm_ref) <= 1e-3 * norm_ref + 1e-12, key
             gp = gp[g[key + "__idx"]]
-        _close(gp, g[key], f"{g.name} {key}")
+        try:
+            _close(gp, g[key], f"{g.name} {key}", mlp)
+        finally:
+            _print_measured(mlp)
         n_checked += 1
     assert n_checked >= 10
 
@@ -362,3 +384,11 @@ def test_weights_changed_forces_the_eval_repack():
     tr.weights_changed()
     r1 = tr.eval_caster().render_rays(rays, m["S"], skts=sk, cyls=cy, N_importance=m["I"])["rgb_map"]
     assert not torch.equal(r0, r1)
+
+
+def test_report_measured_gradient_errors():
+    """A report, not an independent check: last in the module, it prints what the parametrised runs above measured
+    (nothing under a selection that leaves them out); every figure was already asserted where it was measured."""
+    for mlp in GRAD_REL:
+        _print_measured(mlp)
+        assert mlp not in MEASURED or MEASURED[mlp][0] <= GRAD_REL[mlp]
