@@ -26,6 +26,11 @@ from .sequences import (RenderSequence, load_animate, load_bubble, load_bulletti
                         load_interpolate, load_pose_rotate, load_retarget, load_selected, matrix_to_axis_angle,
                         matrix_to_axis_angle_reference, pose_ckpt_to_pose_data, pose_sequence,
                         pose_sequence_reference, render_sequence, write_png)
+from . import posescore
+from .posescore import (PoseScores, Criterion_MPJPE, Criterion3DPose_ProcrustesCorrected,
+                        Criterion3DPose_leastQuaresScaled, evaluate_pampjpe, evaluate_pampjpe_from_smpl_params,
+                        evaluate_pose_ckpt, evaluate_pose_layer, evaluate_poses, evaluate_poses_reference, procrustes,
+                        procrustes_align)
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
@@ -41,4 +46,7 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "sequences", "RenderSequence", "pose_sequence", "pose_sequence_reference", "render_sequence", "write_png",
            "matrix_to_axis_angle", "matrix_to_axis_angle_reference", "pose_ckpt_to_pose_data", "load_retarget",
            "load_bullettime", "load_pose_rotate", "load_interpolate", "load_animate", "load_bubble", "load_selected",
-           "load_correction"]
+           "load_correction", "posescore", "PoseScores", "evaluate_poses", "evaluate_poses_reference",
+           "procrustes_align", "procrustes", "Criterion_MPJPE", "Criterion3DPose_ProcrustesCorrected",
+           "Criterion3DPose_leastQuaresScaled", "evaluate_pampjpe", "evaluate_pampjpe_from_smpl_params",
+           "evaluate_pose_layer", "evaluate_pose_ckpt"]

@@ -363,7 +363,18 @@ SIGNATURES = {
                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
                                             ctypes.c_int32, ctypes.c_int32, c_f, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p]),
+    "anerf_pose_scores_workspace": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "anerf_pose_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_i32p,
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
+                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p]),
 }
+# include/anerf.h ANERF_POSE_*
+ANERF_POSE_PRED_F64, ANERF_POSE_GT_F64, ANERF_POSE_NO_SCALING = 1, 2, 4
+ANERF_POSE_REFLECT_FALSE, ANERF_POSE_REFLECT_TRUE = 8, 16
+ANERF_POSE_MAX_JOINTS, ANERF_POSE_MAX_THRESHOLDS, ANERF_POSE_FRAME_COLS, ANERF_POSE_TOTALS = 128, 64, 25, 520
 ANERF_SEQ_INTERPS = {"linear": 0, "slerp": 1}  # include/anerf.h ANERF_SEQ_*
 ANERF_SEQ_ROOT_KEEP, ANERF_SEQ_ROOT_CONST, ANERF_SEQ_ROOT_COMPOSE = 0, 1, 2
 ANERF_EVAL_BORDERS = {"same": 0, "valid": 1}  # include/anerf.h ANERF_EVAL_*

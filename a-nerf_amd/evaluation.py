@@ -19,7 +19,7 @@ pixels per side, and the mean is the published pytorch_msssim's number.  data_ra
 images; 255.0 gives what the reference's `SSIM(size_average=False)` computes (the package's default range on [0, 1]
 images).
 
-Not covered: writing videos or images, MS-SSIM, LPIPS, the PA-MPJPE pose scores.
+Not covered: writing videos or images, MS-SSIM, LPIPS.  (The pose scores -- MPJPE, PA-MPJPE, PCK -- are posescore.py's.)
 """
 import contextlib
 import os

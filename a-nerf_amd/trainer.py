@@ -751,6 +751,14 @@ class Trainer:
                     "poseopt_anchors": popt_anchors, **ray_caster.module.checkpoint()}, path)
         print("Saved checkpoints at", path)
 
+    def evaluate_poses(self, gt_kps, idxs=None, **kw):
+        """Score the pose layer's current joints against gt_kps [N_kps][J][3] on the device (posescore.
+        evaluate_pose_layer: MPJPE, PA-MPJPE, PCK, AUC) -> PoseScores."""
+        from .posescore import evaluate_pose_layer
+        if self.popt_kwargs is None:
+            raise ValueError("this Trainer optimises no poses (popt_kwargs is None)")
+        return evaluate_pose_layer(self.popt_kwargs["popt_layer"], gt_kps, idxs=idxs, **kw)
+
     def save_popt(self, path, global_step):
         """core/trainer.py:508-516."""
         torch.save({"global_step": global_step,

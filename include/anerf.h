@@ -1131,6 +1131,62 @@ int anerf_sequence_bones(const float* key_bones, const float* key_root, int32_t 
                          int64_t n_frames, int32_t interp, int32_t root_mode, const float* root_const,
                          float* bones_out, float* pelvis_out, void* stream);
 
+/* ---- Scoring refined poses (anerf_posescore.hip; new entries, no struct: ABI 26 still) ---------------------------
+ * MPJPE, root-centred MPJPE, least-squares-scaled MPJPE and the Procrustes-aligned PA-MPJPE of F frames of J joints,
+ * with the counts PCK and its AUC follow from (core/utils/evaluation_helpers.py:387-612: `procrustes`, the three
+ * Criterion* modules, evaluate_pampjpe_from_smpl_params from its line 566 on).  The fit is the reference's
+ * procrustes(X = gt, Y = pred): both centred and divided by their Frobenius norms normX, normY, A = X0^T Y0 = U S V^T,
+ * T = V U^T, trace = sum(S); with scaling b = trace normX / normY and d = 1 - trace^2, without b = 1 and
+ * d = 1 + ssY / ssX - 2 trace normY / normX; Z = b Y T + c, c = muX - b muY T; pa_err = |Z - gt| per joint.
+ * Inputs widen exactly and are multiplied by pred_scale / gt_scale into one unit; everything after is double.  The SVD
+ * is a one-sided cyclic Jacobi with a fixed sweep count.  T is always orthogonal: where A has rank 2 or 1 (singular
+ * values <= 1e-12 of the largest) the missing left singular vectors are completed by cross products to det T = +1
+ * (-1 under ANERF_POSE_REFLECT_TRUE), rank 0 gives T = I; the scores do not depend on the completion.  A frame with
+ * no scored joint, or whose centred sum of squares on either side is <= 1e-26 of the uncentred one (one joint, all
+ * joints equal), has no fit: NaN in pa_mpjpe, d, b, S, T, c, pa_err and aligned, and the totals leave it out. */
+#define ANERF_POSE_PRED_F64 1      /* pred is double (default: float) */
+#define ANERF_POSE_GT_F64 2        /* gt is double */
+#define ANERF_POSE_NO_SCALING 4    /* procrustes(scaling=False) */
+#define ANERF_POSE_REFLECT_FALSE 8 /* procrustes(reflection=False): det T = +1 (Kabsch / Umeyama); default 'best' */
+#define ANERF_POSE_REFLECT_TRUE 16 /* procrustes(reflection=True): det T = -1 */
+#define ANERF_POSE_MAX_JOINTS 128
+#define ANERF_POSE_MAX_THRESHOLDS 64
+/* A frame's record: n, mpjpe, mpjpe_root, n_mpjpe, pa_mpjpe, d, b, S[3], T[3][3] (row-major), c[3], normX (the
+ * extent of gt), normY, s_opt (the least-squares scale of n_mpjpe). */
+#define ANERF_POSE_FRAME_COLS 25
+/* totals, 8-byte words: [0] frames with a fit, [1] those whose root is valid, [2] those with a finite n_mpjpe,
+ * [3..6] the sums of mpjpe, mpjpe_root, n_mpjpe, pa_mpjpe over the frames of [0], [1], [2], [0]; [8 + j] the sum of
+ * err at joint j, [136 + j] of pa_err, [264 + j] the count of scored (frame, joint) pairs at joint j (doubles);
+ * [392 + k] the pairs with pa_err < thresholds[k], [456 + k] those with err < thresholds[k] (int64). */
+#define ANERF_POSE_TOTALS 520
+
+/* Workspace bytes of anerf_pose_scores: the frame records, both error planes and one slot of ANERF_POSE_TOTALS words
+ * per 32 frames (0: refused, see anerf_last_error). */
+size_t anerf_pose_scores_workspace(int32_t n_frames, int32_t n_joints, int32_t n_thresholds);
+/* pred, gt [F][J][3] (device; float, or double under ANERF_POSE_*_F64).  joint_idx: HOST array [n_selected] of the
+ * scored joints (NULL: all; the reference's 17-of-24 lists), valid [F][J] bytes (device; NULL: all ones): a pair
+ * (frame, joint) is scored where the joint is selected and valid.  root: the joint that mpjpe_root and n_mpjpe
+ * subtract from both sides, -1 for none; where it is not valid both are NaN (it need not be selected).  n_mpjpe scales
+ * pred by s_opt = <pred, gt> / <pred, pred> over the root-centred scored joints.  thresholds: HOST array.
+ *   totals [ANERF_POSE_TOTALS] (device): as above, over the frames with a fit; a frame's means are over its scored
+ *     joints.
+ *   frames [F][ANERF_POSE_FRAME_COLS], err [F][J], pa_err [F][J] (device, double, each may be NULL: kept in the
+ *     workspace): the records and the error planes, 0 at joints that are not scored (err is set in frames without a
+ *     fit too).  aligned [F][J][3] (device, float, may be NULL): Z of every joint, rounded once.
+ * A wavefront scores a frame, lane l holding joints l and l + 64 in joint order, with one __shfl_xor butterfly per
+ * sum; a workgroup per 32 frames adds its slot and a last workgroup the slots in order: no atomics, the same bits
+ * on every run, a frame's record the same whatever other frames are in the call.  Allocation-free, asynchronous on
+ * `stream`, no host read.  n_frames == 0 returns ANERF_OK without a launch (totals is not written).  ANERF_EINVAL,
+ * before any HIP call, for a NULL pred, gt, totals or workspace, n_frames < 0, n_joints outside [1, 128], root
+ * outside [-1, J), a joint_idx entry outside [0, J) or repeated, n_selected outside [0, J], more than 64 thresholds
+ * (or thresholds NULL with n_thresholds > 0), unknown flag bits or both REFLECT flags, a scale that is not finite, a
+ * workspace not 8-byte aligned; ANERF_EWORKSPACE for a workspace that is too small. */
+int anerf_pose_scores(const void* pred, const void* gt, int32_t n_frames, int32_t n_joints, const int32_t* joint_idx,
+                      int32_t n_selected, const uint8_t* valid, int32_t root, double pred_scale, double gt_scale,
+                      int32_t flags, const double* thresholds, int32_t n_thresholds, double* totals, double* frames,
+                      double* err, double* pa_err, float* aligned, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
