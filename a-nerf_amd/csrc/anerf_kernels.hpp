@@ -94,7 +94,10 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
             // (5.8 % of the wave-cycles, profiles/r04c_stamps_bf16x6.txt).  The blocks of the workgroup
             // run in ascending order of their live-joint counts, so the four blocks of an iteration have
             // about equal windowed work.  (Outputs are unchanged: a block's arithmetic does not depend on
-            // the wave that runs it.)
+            // the wave that runs it.)  Ties go by depth index, then ray: the same depth range of the item's
+            // adjacent pixels is empty together, so an iteration's four blocks tend to be dead together
+            // (mlp_block's skip_dead), and only then does the iteration end sooner: a wave that skips
+            // alone waits at the next block's first barrier.
             for (int b = wave; b < nbt; b += 4) {
                 const int r = b / nb;
                 const int c = block_live_count(M, lds + P.ray + 16 * r, lds + P.sk + P.sk_stride * r, lds + P.cut,
@@ -103,11 +106,11 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
             }
             __syncthreads();
             for (int i = tid; i < nbt; i += blockDim.x) {
-                const int ci = bcnt[i];
+                const int ci = bcnt[i], ki = (i % nb) * nr + i / nb;
                 int rank = 0;
                 for (int j = 0; j < nbt; ++j) {
-                    const int cj = bcnt[j];
-                    rank += (cj < ci) | ((cj == ci) & (j < i));
+                    const int cj = bcnt[j], kj = (j % nb) * nr + j / nb;
+                    rank += (cj < ci) | ((cj == ci) & (kj < ki));
                 }
                 bord[rank] = i;
             }
@@ -128,7 +131,7 @@ __device__ __forceinline__ void render_item(const ModelDev& M, const RenderArgs&
             mlp_block<W, MR, PREC, !FUSED>(M, net, lds + P.ray + 16 * r, lds + P.sk + P.sk_stride * r, lds + P.cut,
                              zr, nm, s0, lds + P.g + P.g_stride * r, rawr, lane, own ? A.mfma_count : nullptr,
                              lds + P.bias, (P.uf >= 0 && M.skip + 1 < M.D) ? lds + P.uf + wave * P.uf_stride : nullptr,
-                             lds + P.wv + wave * P.wv_stride, st, own);
+                             lds + P.wv + wave * P.wv_stride, st, own, A.skip_dead != 0);
         }
         STAMP(st, 2 + 2 * pass);
         if constexpr (!FUSED) break;  // (one pass per launch; the kernel's item loop has the barrier before the next item)

@@ -1568,15 +1568,62 @@ __device__ __forceinline__ bool mlp_trunk(const ModelDev& M, const NetDev& net, 
     return pre6;  // (bf16x6 / fp16x3: after_last's first groups are in the ring)
 }
 
+// The density activation of raw2outputs on sigma / B (composite(), anerf_stages.hpp; mlp_block's dead test)
+__device__ __forceinline__ float density_act(const ModelDev& M, float x) {
+    if (!M.softplus) return relu(x);
+    const float y = x - M.shift;  // F.softplus(beta=1, threshold=20)
+    return y > 20.0f ? y : log1pf(expf(y));
+}
+
+// The alpha head on the last hidden layer's accumulators, ahead of the view layer: the view layer's fold
+// (mlp_layer*'s ALPHA) as a pass of its own, the same operations in the same order -- one fmaf chain over
+// k = 16 ib + 8 s + j on relu_act(acc), the fp16 modes' unscale 2^-es_h, the wave halves' sum, + balpha -- so
+// sigma keeps its bits.  wa: w_alpha in LDS, [2][RB][16].
+template <int RB, int P>
+__device__ __forceinline__ float alpha_head(const f32x16 (&acc)[RB], const float* __restrict__ wa, int hh, int es_h,
+                                            float balpha) {
+    float sig = 0.0f;
+#pragma unroll
+    for (int ib = 0; ib < RB; ++ib) {
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(wa + hh * 16 * RB + 16 * ib);
+        const f32x4 u0 = w4[0], u1 = w4[1], u2 = w4[2], u3 = w4[3];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float w = i < 4 ? u0[i & 3] : (i < 8 ? u1[i & 3] : (i < 12 ? u2[i & 3] : u3[i & 3]));
+            sig = fmaf(w, relu_act(acc[ib][i]), sig);
+        }
+    }
+    if constexpr (P >= 3) {
+        sig *= pow2f(-es_h);
+        sig = sum_halves(sig);
+    } else {
+        sig += __shfl_xor(sig, 32);
+    }
+    return sig + balpha;
+}
+
+// Instances whose mlp_block forms sigma ahead of the view layer (alpha_head) and may skip the colour branch of
+// a dead block; the others keep the fold.  FUSED: render_fused_kernel (single_net).  Its fp32, bf16x3 and
+// bf16x6 instances keep the fold: with the accumulators in AGPRs the pass ahead of the view layer took them
+// to 512 registers and 24 - 136 B of scratch (the other instances: profiles/dead_block_skip_ab.txt).
+template <int P, bool FUSED>
+__host__ __device__ constexpr bool alpha_first_mode() {
+    return P >= 3 || !FUSED;
+}
+
 // One 32-sample block of one ray through a whole NeRF: raw (rgb, sigma) into LDS, or (GRAW) into the workspace's
 // raw array (raw_out 16-byte aligned), one 16-byte store per sample.
+// skip_dead (wave-uniform; the host clears it for softplus densities and for diagnostic calls): a block whose 32
+// samples all have density_act(sigma / B) == 0 stores (0, 0, 0, sigma) and leaves out the view layer, the
+// view-direction part and the rgb head.  Such a sample's alpha is exactly +0 (composite()), so its weight is 0
+// and its colour term +-0: no output depends on its rgb raws.  A NaN sigma compares unequal and keeps the block live.
 template <int W, int MR, int P, bool GRAW = false>
 __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __restrict__ ray,
                           const float* __restrict__ sk, const float* __restrict__ cut, const float* __restrict__ z,
                           int n, int s0,
                           const float* __restrict__ G, float* __restrict__ raw_out, int lane,
                           unsigned long long* mfma_count, const float* __restrict__ bias, float* __restrict__ uf,
-                          float* __restrict__ wvp, Stamps& st, bool store = true) {
+                          float* __restrict__ wvp, Stamps& st, bool store = true, bool skip_dead = false) {
     constexpr int RB = W / 32;
     constexpr int RBV = (W / 2) / 32;
     const int sl = lane & 31, hh = lane >> 5;
@@ -1597,24 +1644,64 @@ __device__ void mlp_block(const ModelDev& M, const NetDev& net, const float* __r
     // views_linears.0 with feature_linear fused in (W' = Wv_f Wf, see pack_net) on relu(h_last),
     // alpha_linear folded into its groups (same relu'd B operands), + the factorised
     // direction / code / bias part from G, then relu
+    constexpr bool FOLD = !alpha_first_mode<P, !GRAW>();  // the alpha head folded into the view layer's groups
     float sig = 0.0f;
+    if constexpr (!FOLD) {
+        sig = alpha_head<RB, P>(acc, bias + (M.D + 1) * W, hh, es, net.balpha);
+        if (skip_dead) {
+            // wave-uniform (a scalar branch): no lane with a density other than zero; lanes past n repeat sample n - 1
+            const bool live = !(density_act(M, sig / M.B) == 0.0f);
+            bool dead = __builtin_amdgcn_ballot_w64(live) == 0;
+            if (dead) {
+                // A NaN or infinity in what only the colour branch reads -- the ray's view factor G (NaN transforms
+                // of an out-of-range pose index) or the block's view windows -- gives NaN rgb raws, and 0 * NaN is
+                // the NaN that such a ray's rgb map is: the block stays live.  (A NaN in the hidden activations
+                // reaches sigma by the alpha head.)  x * 0 summed: +0 unless some x is not finite.
+                float t = 0.0f;
+                for (int p = 0; p < M.njh2; ++p) t = fmaf(wvp[p * 64 + lane], 0.0f, t);
+                for (int p = 0; p <= M.njh2; ++p) {
+                    const int c = p < M.njh2 ? p + hh * M.njh2 : M.nj + hh;  // view_dir_part's columns
+#pragma unroll
+                    for (int rb = 0; rb < RBV; ++rb) t = fmaf(G[c * (RBV * 32) + sl + 32 * rb], 0.0f, t);
+                }
+                dead = __builtin_amdgcn_ballot_w64(t != 0.0f) == 0;
+            }
+            if (dead) {
+                // (the view weights prefetched into the ring are dropped; the hidden layers' barriers are all behind)
+                if (store && hh == 0 && s0 + sl < n) {
+                    float* o = raw_out + 4 * (s0 + sl);
+                    if constexpr (GRAW) {
+                        const f32x4 v = {0.0f, 0.0f, 0.0f, sig};
+                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o));
+                    } else {
+                        o[0] = o[1] = o[2] = 0.0f;
+                        o[3] = sig;
+                    }
+                }
+                return;
+            }
+        }
+    }
     f32x16 av[RBV];
+    float nosig = 0.0f;
     if constexpr (P >= 3) {
         const int es_h = es;  // the alpha head sums the last hidden layer's activations, in its units
-        mlp_layer_h3<RBV, RB, false, true, P == 4 ? 4 : 3>(av, acc, h, nullptr, net.wviewh, lane, ring, pre, nullptr,
-                                           bias + (M.D + 1) * W, sig, es, net.ew_view, M.h3_top);
-        sig *= pow2f(-es_h);
+        mlp_layer_h3<RBV, RB, false, FOLD, P == 4 ? 4 : 3>(av, acc, h, nullptr, net.wviewh, lane, ring, pre, nullptr,
+                                           bias + (M.D + 1) * W, FOLD ? sig : nosig, es, net.ew_view, M.h3_top);
+        if constexpr (FOLD) sig *= pow2f(-es_h);
     } else if constexpr (P == 2)
-        mlp_layer_x6<RBV, RB, false, true>(av, acc, h, nullptr, net.wview6, lane, ring, pre, nullptr,
-                                           bias + (M.D + 1) * W, sig);
+        mlp_layer_x6<RBV, RB, false, FOLD>(av, acc, h, nullptr, net.wview6, lane, ring, pre, nullptr,
+                                           bias + (M.D + 1) * W, FOLD ? sig : nosig);
     else
-        mlp_layer<RBV, RB, true, false, true>(av, acc, h, nullptr, net.wview, lane, ring, nullptr,
-                                              bias + (M.D + 1) * W, sig);
+        mlp_layer<RBV, RB, true, false, FOLD>(av, acc, h, nullptr, net.wview, lane, ring, nullptr,
+                                              bias + (M.D + 1) * W, FOLD ? sig : nosig);
     STAMP(st, 16);
-    // (the fp16 modes: in the VALU; the other modes' instances keep the code they were measured with)
-    if constexpr (P >= 3) sig = sum_halves(sig);
-    else sig += __shfl_xor(sig, 32);
-    sig += net.balpha;
+    if constexpr (FOLD) {
+        // (the fp16 modes: in the VALU; the other modes' instances keep the code they were measured with)
+        if constexpr (P >= 3) sig = sum_halves(sig);
+        else sig += __shfl_xor(sig, 32);
+        sig += net.balpha;
+    }
     const int vsteps = view_dir_part<RBV>(av, M, G, wvp, reinterpret_cast<const unsigned*>(ray) + 12, lane,
                                           P >= 3 ? pow2f(es) : 1.0f);
     STAMP(st, 17);

@@ -439,6 +439,9 @@ int anerf_render_rays(const anerf_model* m, const float* ray_batch, int32_t ray_
     a.alpha = alpha;
     a.alpha0 = alpha0;
     a.lindisp = (flags & ANERF_FLAG_LINDISP) ? 1 : 0;
+    // off for softplus (the density is never 0) and for a diagnostic call: raw_coarse / raw_fine hold every
+    // sample's real rgb raws and the MFMA tally counts every view branch
+    a.skip_dead = (!debug && !m->md.softplus) ? 1 : 0;
     if (debug) {
         a.dbg_z0 = debug->z_coarse;
         a.dbg_raw0 = debug->raw_coarse;

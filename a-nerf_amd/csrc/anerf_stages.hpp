@@ -176,12 +176,6 @@ __device__ void compute_view_factor(const ModelDev& M, const NetDev& net, float*
     __syncthreads();
 }
 
-__device__ __forceinline__ float density_act(const ModelDev& M, float x) {
-    if (!M.softplus) return relu(x);
-    const float y = x - M.shift;  // F.softplus(beta=1, threshold=20)
-    return y > 20.0f ? y : log1pf(expf(y));
-}
-
 // raw2outputs (nerf.py:150-205) of ray slot r over n samples; wave-cooperative, all waves call it.
 // scr layout: w[zs], wz[zs], wc[3 zs], fac[zs], al[zs]
 // Results (rgb[3], disp, acc) are left in res[0..4] (LDS) for the caller to store.

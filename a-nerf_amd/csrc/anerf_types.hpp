@@ -121,6 +121,7 @@ struct RenderArgs {
     float* raw_ws;     // n x (this launch's samples) x 4: the raws of a launch that ends there, for the stage kernels
     int lindisp;       // sample_from_lineseg in inverse depth (ANERF_FLAG_LINDISP)
     unsigned* queue;   // this launch's 8 band counters (persistent workgroups) (workspace, zeroed before the launch)
+    int skip_dead;     // mlp_block leaves out the colour branch of blocks with zero density (product calls, relu density)
 };
 
 // ======================================================================= LDS plan

@@ -261,7 +261,11 @@ typedef struct {
                                        work (agrees with PMC SQ_INSTS_MFMA): [0] v_mfma_f32_32x32x2_f32,
                                        [1] the 16-bit MFMAs, v_mfma_f32_32x32x16_bf16 (bf16x3 / bf16x6
                                        modes, and the bf16x6 bone-direction parts of fp16x3) and
-                                       v_mfma_f32_32x32x16_f16 (fp16x3), the same FLOPs and cycles each */
+                                       v_mfma_f32_32x32x16_f16 (fp16x3), the same FLOPs and cycles each.
+                                       The tally is a diagnostic call's (debug != NULL), which runs every
+                                       32-sample block in full; a product call (debug == NULL, relu density)
+                                       issues fewer MFMAs by the view layer and view-direction part of the
+                                       blocks whose 32 densities are all zero, which it leaves out */
 } anerf_debug;
 
 int anerf_abi_version(void);

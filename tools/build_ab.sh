@@ -10,7 +10,7 @@ NAME=$1; shift
 C=a-nerf_amd/csrc
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wno-unused-result"
 OTHER=""
-for u in gemm iso mesh raster; do
+for u in gemm iso mesh raster simplify step eval sequence posescore; do  # (every other unit of build.py's SRC)
   o=tools/ab/$u.o
   [ -f $o ] && [ $o -nt $C/anerf_$u.hip ] && [ $o -nt $C/anerf_scan.hpp ] && [ $o -nt $C/anerf_iso_table.inc ] && [ $o -nt include/anerf.h ] ||
     /opt/rocm/bin/hipcc $F -c -o $o $C/anerf_$u.hip
