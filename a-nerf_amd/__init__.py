@@ -31,6 +31,13 @@ from .posescore import (PoseScores, Criterion_MPJPE, Criterion3DPose_ProcrustesC
                         Criterion3DPose_leastQuaresScaled, evaluate_pampjpe, evaluate_pampjpe_from_smpl_params,
                         evaluate_pose_ckpt, evaluate_pose_layer, evaluate_poses, evaluate_poses_reference, procrustes,
                         procrustes_align)
+from . import preprocess
+from .preprocess import (create_kp_mask, create_kp_masks, create_kp_masks_reference, dilate_masks,
+                         dilate_masks_reference, draw_segments, draw_segments_reference, draw_skeleton2d,
+                         draw_skeletons, draw_skeletons_3d, draw_skeletons_3d_reference, draw_skeletons_reference,
+                         erode_masks, erode_masks_reference, mask_morph, mask_morph_reference, median_backgrounds,
+                         median_backgrounds_reference, prepare_dataset, sampling_masks, sampling_masks_reference,
+                         skeleton3d_to_2d, skeleton3d_to_2d_reference)
 
 __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "render", "render_path",
            "render_frames", "batchify_rays", "rays", "synthetic", "dataset", "RayImageDataset", "RayImageSampler", "flops_per_sample", "samples_per_ray",
@@ -49,4 +56,9 @@ __all__ = ["RenderConfig", "RayCaster", "create_raycaster", "load_checkpoint", "
            "load_correction", "posescore", "PoseScores", "evaluate_poses", "evaluate_poses_reference",
            "procrustes_align", "procrustes", "Criterion_MPJPE", "Criterion3DPose_ProcrustesCorrected",
            "Criterion3DPose_leastQuaresScaled", "evaluate_pampjpe", "evaluate_pampjpe_from_smpl_params",
-           "evaluate_pose_layer", "evaluate_pose_ckpt"]
+           "evaluate_pose_layer", "evaluate_pose_ckpt", "preprocess", "dilate_masks", "erode_masks", "sampling_masks",
+           "mask_morph", "draw_segments", "skeleton3d_to_2d", "draw_skeleton2d", "draw_skeletons", "draw_skeletons_3d",
+           "create_kp_masks", "create_kp_mask", "median_backgrounds", "prepare_dataset", "mask_morph_reference",
+           "dilate_masks_reference", "erode_masks_reference", "sampling_masks_reference", "draw_segments_reference",
+           "draw_skeletons_reference", "draw_skeletons_3d_reference", "skeleton3d_to_2d_reference",
+           "create_kp_masks_reference", "median_backgrounds_reference"]

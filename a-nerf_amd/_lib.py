@@ -370,7 +370,20 @@ SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
+    "anerf_mask_morph": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "anerf_draw_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "anerf_background_median": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                               c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
+# include/anerf.h ANERF_MORPH_*, ANERF_PREP_*
+ANERF_MORPH_DILATE, ANERF_MORPH_ERODE = 0, 1
+ANERF_PREP_MAX_RADIUS, ANERF_PREP_MAX_DIM, ANERF_PREP_MAX_SEGMENTS, ANERF_PREP_MAX_COORD = 32, 32768, 128, 8192
+ANERF_PREP_MAX_WIDTH, ANERF_PREP_MAX_CAMERA_FRAMES = 4096, 1 << 20
 # include/anerf.h ANERF_POSE_*
 ANERF_POSE_PRED_F64, ANERF_POSE_GT_F64, ANERF_POSE_NO_SCALING = 1, 2, 4
 ANERF_POSE_REFLECT_FALSE, ANERF_POSE_REFLECT_TRUE = 8, 16

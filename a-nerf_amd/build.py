@@ -5,7 +5,8 @@ include/anerf.h is stored next to the library (`libanerf_hip.so.stamp`).  A ship
 stamp does not match the sources is rebuilt, never reused because of its mtime.
 
 The translation units compile in parallel into objects cached under `.objs/` by the hash of
-their own dependencies (anerf_gemm.hip, anerf_step.hip, anerf_eval.hip, anerf_sequence.hip and anerf_posescore.hip read only include/anerf.h; anerf_iso.hip, anerf_mesh.hip, anerf_raster.hip
+their own dependencies (anerf_gemm.hip, anerf_step.hip, anerf_eval.hip, anerf_sequence.hip, anerf_posescore.hip and
+anerf_prep.hip read only include/anerf.h; anerf_iso.hip, anerf_mesh.hip, anerf_raster.hip
 and anerf_simplify.hip that and csrc/anerf_scan.hpp, which no other unit reads, anerf_iso.hip also its case table),
 then link into the library: an edit of the training GEMMs, of the iso-surface, of the mesh, of the raster or of the
 simplification kernels recompiles one unit, an edit of their shared scan header those four, never the render kernels'
@@ -27,7 +28,8 @@ SRC = [os.path.join(CSRC, "anerf_render.hip"), os.path.join(CSRC, "anerf_render_
        os.path.join(CSRC, "anerf_iso.hip"), os.path.join(CSRC, "anerf_mesh.hip"),
        os.path.join(CSRC, "anerf_raster.hip"), os.path.join(CSRC, "anerf_simplify.hip"),
        os.path.join(CSRC, "anerf_step.hip"), os.path.join(CSRC, "anerf_eval.hip"),
-       os.path.join(CSRC, "anerf_sequence.hip"), os.path.join(CSRC, "anerf_posescore.hip")]
+       os.path.join(CSRC, "anerf_sequence.hip"), os.path.join(CSRC, "anerf_posescore.hip"),
+       os.path.join(CSRC, "anerf_prep.hip")]
 # anerf_iso.hip's, anerf_mesh.hip's, anerf_raster.hip's and anerf_simplify.hip's alone
 SCAN_HEADER = os.path.join(CSRC, "anerf_scan.hpp")
 OUT = os.path.join(HERE, "libanerf_hip.so")
@@ -65,12 +67,13 @@ def source_hash():
 
 
 def unit_deps(src):
-    """The files a translation unit reads: anerf_gemm.hip, anerf_step.hip, anerf_eval.hip, anerf_sequence.hip and
-    anerf_posescore.hip only the C header; anerf_mesh.hip, anerf_raster.hip,
+    """The files a translation unit reads: anerf_gemm.hip, anerf_step.hip, anerf_eval.hip, anerf_sequence.hip,
+    anerf_posescore.hip and anerf_prep.hip only the C header; anerf_mesh.hip, anerf_raster.hip,
     anerf_simplify.hip and anerf_iso.hip the scan header and the C header, anerf_iso.hip its case table as well;
     anerf_render.hip and anerf_render_f16.hip every other csrc header."""
     name = os.path.basename(src)
-    if name in ("anerf_gemm.hip", "anerf_step.hip", "anerf_eval.hip", "anerf_sequence.hip", "anerf_posescore.hip"):
+    if name in ("anerf_gemm.hip", "anerf_step.hip", "anerf_eval.hip", "anerf_sequence.hip", "anerf_posescore.hip",
+                "anerf_prep.hip"):
         return [src, HEADER]
     if name in ("anerf_mesh.hip", "anerf_raster.hip", "anerf_simplify.hip"):
         return [src, SCAN_HEADER, HEADER]

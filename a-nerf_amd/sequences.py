@@ -16,7 +16,7 @@ tests/golden/sequences.npz holds the reference loaders' own outputs.
 
 Beyond the reference: `interp="slerp"` interpolates per joint on the rotation group (the lerp of axis-angle vectors
 leaves the geodesic and jumps where two keys sit on either side of pi), any tree skeleton up to 128 joints.
-Not covered: reading h5 files, mp4 writing, the skeleton overlay, the perfcap `/ 1.05` camera quirk (divide
+Not covered: reading h5 files, mp4 writing, the perfcap `/ 1.05` camera quirk (divide
 `render_poses[..., :3, -1]`), gradients through the sequence layer.
 """
 import math
@@ -30,6 +30,7 @@ import torch
 from . import _lib
 from . import rays as host_rays
 from .kinematics import PoseOptLayer, SMPLSkeleton, matrix_to_axis_angle, pose_kinematics
+from .preprocess import draw_skeletons_3d
 from .render import render_frames
 
 KINDS = ("selected", "retarget", "bullet", "poserot", "interpolate", "animate", "bubble", "correction")
@@ -751,11 +752,13 @@ def read_png(path):
 
 @torch.no_grad()
 def render_sequence(seq, H, W, chunk, render_kwargs, *, white_bkgd=False, bg_imgs=None, bg_indices=None,
-                    ret_acc=False, ext_scale=0.00035, to_uint8=True, to_host=False, out_dir=None):
+                    ret_acc=False, ext_scale=0.00035, to_uint8=True, to_host=False, out_dir=None, skeleton=False):
     """Render every frame of a RenderSequence at H x W -> (rgbs (F, H, W, 3), disps (F, H, W, 1), accs (F, H, W, 1) or
     [] without ret_acc): device tensors (NumPy with to_host), rgbs as uint8 through to8b with to_uint8.  The frames
     come from render_frames(..., to_host=False) on the sequence's device tensors.  With out_dir the 8-bit frames are
-    also written there as %05d.png."""
+    also written there as %05d.png.  With skeleton a fourth value follows: the 8-bit frames with the sequence's
+    joints drawn through its cameras (run_render.py:1032-1043; preprocess.draw_skeletons_3d), written as
+    skel/%05d.png under out_dir."""
     kw = seq.render_kwargs(H, W)
     frames, _, _ = render_frames(kw["render_poses"], kw["hwf"], chunk, render_kwargs, kp=kw["kp"], skts=kw["skts"],
                                  bones=kw["bones"], cams=kw["cams"], bg_imgs=bg_imgs, bg_indices=bg_indices,
@@ -763,16 +766,26 @@ def render_sequence(seq, H, W, chunk, render_kwargs, *, white_bkgd=False, bg_img
     rgbs = torch.stack([f[0] for f in frames], 0)
     disps = torch.stack([f[1] for f in frames], 0)
     accs = torch.stack([f[2] for f in frames], 0) if ret_acc else []
-    rgb8 = to8b(rgbs) if (to_uint8 or out_dir is not None) else None
+    rgb8 = to8b(rgbs) if (to_uint8 or skeleton or out_dir is not None) else None
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         for i, img in enumerate(rgb8.cpu().numpy()):
             write_png(os.path.join(out_dir, f"{i:05d}.png"), img)
+    skels = None
+    if skeleton:
+        skels = draw_skeletons_3d(rgb8, seq.kp, kw["render_poses"], *kw["hwf"])
+        if out_dir is not None:
+            os.makedirs(os.path.join(out_dir, "skel"), exist_ok=True)
+            for i, img in enumerate(skels.cpu().numpy()):
+                write_png(os.path.join(out_dir, "skel", f"{i:05d}.png"), img)
     if to_uint8:
         rgbs = rgb8
     if to_host:
         rgbs, disps = rgbs.cpu().numpy(), disps.cpu().numpy()
         accs = accs.cpu().numpy() if ret_acc else []
+        skels = skels.cpu().numpy() if skeleton else None
+    if skeleton:
+        return rgbs, disps, accs, skels
     return rgbs, disps, accs
 
 

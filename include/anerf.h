@@ -1191,6 +1191,65 @@ int anerf_pose_scores(const void* pred, const void* gt, int32_t n_frames, int32_
                       double* err, double* pa_err, float* aligned, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- Making a dataset: masks, skeleton segments, median backgrounds (anerf_prep.hip; new entries, no struct: ABI 26
+ * still) ------------------------------------------------------------------------------------------------------------
+ * The pixel-level steps of the reference's loaders (dilate_masks, get_mask, create_kp_mask, draw_skeleton2d, the
+ * per-camera median backgrounds) on byte images where they lie.  Every decision is an integer decision, no entry uses
+ * atomics, and each gives the same bits on every run.  All three are allocation-free and asynchronous on `stream`,
+ * validate before any launch (ANERF_EINVAL with anerf_last_error) and read nothing back. */
+#define ANERF_MORPH_DILATE 0 /* maximum over the window */
+#define ANERF_MORPH_ERODE 1  /* minimum over the window */
+#define ANERF_PREP_MAX_RADIUS 32
+#define ANERF_PREP_MAX_DIM 32768
+#define ANERF_PREP_MAX_SEGMENTS 128
+#define ANERF_PREP_MAX_COORD 8192 /* anerf_draw_segments: H, W and the magnitude of an endpoint's coordinates */
+#define ANERF_PREP_MAX_WIDTH 4096
+#define ANERF_PREP_MAX_CAMERA_FRAMES (1 << 20) /* anerf_background_median: frames in one camera's list (int32 counters) */
+
+/* src, dst [n_masks][H][W] bytes (device, any values; dst must not be src).  dst = the maximum (ANERF_MORPH_DILATE) or
+ * minimum (ANERF_MORPH_ERODE) of src over the square window of half-width `radius` around each pixel; window
+ * positions outside the mask are ignored (cv2's default morphology border).  `iterations` applications of a k x k
+ * all-ones element, k odd, are one window of radius iterations (k - 1) / 2.  radius 0 copies.
+ *   band > 0 (with ANERF_MORPH_DILATE; load_zju.py's get_mask): afterwards dst = 0 wherever
+ *     (uint8)(dilate(src, band) - erode(src, band)) == 1.
+ *   other != NULL ([n_masks][H][W] bytes; may be dst): afterwards dst = (dst != 0) | (other != 0) as 0 / 1 bytes.
+ * One separable pass over an LDS tile with a halo of max(radius, band): a pixel costs O(radius + band).
+ * ANERF_EINVAL for a NULL src or dst, dst == src, an unknown op, n_masks < 0, H or W outside [1, 32768], radius or
+ * band outside [0, 32], a band with ANERF_MORPH_ERODE, n_masks x tiles (64 x 32 pixels each) >= 2^31. */
+int anerf_mask_morph(const uint8_t* src, uint8_t* dst, int64_t n_masks, int32_t H, int32_t W, int32_t op,
+                     int32_t radius, int32_t band, const uint8_t* other, void* stream);
+
+/* segs [n_frames][n_segs][4] int32 (device): the endpoints (px, py, qx, qy) of each frame's segments.  Segment b covers
+ * the pixel with integer centre c iff the squared distance from c to the closed segment [p, q] is <= (width / 2)^2,
+ * decided in int64 with d = q - p, e = c - p, t = e . d:
+ *   t <= 0: 4 |c - p|^2 <= width^2;  t >= |d|^2: 4 |c - q|^2 <= width^2;  else 4 cross(d, e)^2 <= width^2 |d|^2.
+ * A zero-length segment is a disc.  Where several segments cover a pixel the highest index wins.  A segment with an
+ * endpoint coordinate outside [-8192, 8192] is dropped (not clamped).  With H, W <= 8192 every coordinate difference
+ * is at most 2^14 in magnitude, so |t|, |d|^2 <= 2^29, |cross| < 2^29, the left sides stay under 2^60 and, with
+ * width <= 4096, the right side under 2^53: exact.
+ *   mask   [n_frames][H][W] bytes (device, may be NULL): 1 where a segment covers, else 0 (every pixel is written).
+ *   frames [n_frames][H][W][3] bytes (device, may be NULL): painted in place, a covered pixel takes colors[b]
+ *     (colors [n_segs][3] bytes, device) of the winning segment, every other byte is left as it is.
+ * The result does not depend on the schedule (a workgroup per 32 x 16 tile and frame, the frame's segments culled
+ * against the tile).  ANERF_EINVAL for neither output, frames without colors, n_frames < 0, n_segs outside [0, 128],
+ * segs NULL with n_segs > 0, H or W outside [1, 8192], width outside [1, 4096], n_frames x tiles >= 2^31. */
+int anerf_draw_segments(const int32_t* segs, int32_t n_frames, int32_t n_segs, int32_t H, int32_t W, int32_t width,
+                        const uint8_t* colors, uint8_t* mask, uint8_t* frames, void* stream);
+
+/* imgs [n_imgs][n_pixels][3] bytes, masks [n_imgs][n_pixels] bytes or NULL (device).  Camera c's frames are
+ * order[cam_start[c] .. cam_start[c + 1]) (order [M] and cam_start [n_cams + 1] int32, both given twice: on the host,
+ * checked here, and on the device, read by the kernel; the caller uploads them once).  For every camera, pixel and
+ * channel: of the listed frames (with masks: those whose mask byte at the pixel is 0) with n taken and their values
+ * v ascending, bkgds = floor((v[(n - 1) / 2] + v[n / 2]) / 2), which is np.median(...).astype(np.uint8); n == 0 gives 0.
+ *   bkgds [n_cams][n_pixels][3] bytes, counts [n_cams][n_pixels] int32 or NULL: n (device).
+ * A thread per (camera, pixel) bisects on the value with int32 counters: a camera lists at most
+ * ANERF_PREP_MAX_CAMERA_FRAMES frames.  ANERF_EINVAL for a NULL imgs, bkgds or cam_start, n_imgs outside [0, 2^31),
+ * n_pixels outside [1, 2^30], n_cams outside [0, 65535], cam_start[0] != 0 or decreasing, a camera over the limit, order
+ * NULL with M > 0, an order entry outside [0, n_imgs): the kernel never sees an index out of range. */
+int anerf_background_median(const uint8_t* imgs, const uint8_t* masks, int64_t n_imgs, int64_t n_pixels,
+                            const int32_t* order_host, const int32_t* cam_start_host, const int32_t* order,
+                            const int32_t* cam_start, int32_t n_cams, uint8_t* bkgds, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
